@@ -8,10 +8,11 @@ B = 64 videos x 4 clips/GPU, Lc = Lv = 80 frames, Ls = 16 / Lp = 64 tokens, Dv =
 bf16 MFMA operands, fp32 accumulation/statistics/master weights; dropout ON as in training).  Inputs are
 resident in HBM before the timed region.  Weak scaling: per-GPU batch fixed, global batch = 64 N videos.
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload anet|yc2_100m|yc2_2d3d|yc2_2d3d_2816|hbm_stress]
+    python bench.py [--gpus N --steps K --warmup W] [--workload anet|yc2_100m|yc2_2d3d|yc2_2d3d_2816|hbm_stress] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K steps and prints it;
+--dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy (dump_outputs).  With --full the line also holds
   "roofline": the MFMA kernel family the step spends most time in (the fused token-tile chains: infc_qkv_fwd, post_attn_fwd,
               pre_attn_bwd, qkv_bwd), algorithmic FLOP/s from HIP events on the launch stream vs 2.5 PF dense bf16;
               for --workload hbm_stress the input LayerNorm (the kernel that reads the feature stream) vs 8 TB/s HBM;
@@ -38,8 +39,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="anet")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure what the headline figure does not need: the "
+                    "roofline (extra instrumented steps) and, with one rank, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, "
+                    "<= 64 MB in all): the losses and every network's parameters after the update (eval: the embeddings)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave the roofline out")
     ap.add_argument("--opt", action="append", default=[], help="library A/B switch name=value (coot_set_option), repeatable")
     ap.add_argument("--force-dp", action="store_true", help="run the data-parallel step (phase calls + RCCL collectives) even with one rank")
     ap.add_argument("--dp-backend", default="nccl", choices=["nccl", "gloo"], help="process-group backend of the data-parallel step: nccl = RCCL over xGMI "
@@ -53,6 +58,8 @@ def parse():
     ap.add_argument("--clock-monitor", action="store_true", help="after the timed loop: sample the shader clock on a side stream while more steps run (stderr)")
     ap.add_argument("--no-lookahead", action="store_true", help="do not announce the next batch to the step: its input LayerNorm runs at the head of its own step instead of next to the previous step's global networks (A/B)")
     ap.add_argument("--no-defer-join", action="store_true", help="join the text stream into the main stream at the end of every step (A/B)")
+    ap.add_argument("--nondeterministic", action="store_true", help="train step without the deterministic mode (RetrievalTrainer.set_deterministic): "
+                    "the library's few fp32 atomic sums in arrival order, so two runs of the same arguments compute different trajectories (A/B)")
     ap.add_argument("--repeat", type=int, default=1, help="regime probe: time R blocks of K steps back to back (each bracketed like the first); the JSON "
                     "line is the FIRST block (the contract's), the others go to stderr and to 'blocks_ms_per_step'")
     ap.add_argument("--per-step-events", action="store_true", help="regime probe: a timing event on the main stream behind every step (warm-up "
@@ -158,6 +165,25 @@ def cpu_baseline(w, budget_s=22.0, budget_1t_s=10.0):
                       f"({int(clips1)} clips), median of {n1} steps, {dt1:.3f} s/step"}
 
 
+def dump_outputs(dirname, out, mgr, eval_mode):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy.  Train: the three losses it returns (float64) and
+    every network's parameters after its update (the flat fp32 arena, ~30 MB for all four).  Eval: the four embedding matrices.  Inputs,
+    weights and dropout masks are seeded and the train step runs in deterministic mode: the same arguments write the same arrays."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {}
+    if eval_mode:
+        _, v, t = out
+        for name, x in (("vid_emb", v.vid_emb), ("clip_emb", v.clip_emb), ("par_emb", t.par_emb), ("sent_emb", t.sent_emb)):
+            arrays[name] = x.detach().float().cpu().numpy()
+    else:
+        arrays["losses"] = np.array([float(x) for x in out[:3]], dtype=np.float64)  # total, contrastive, cycle-consistency
+        for key, net in mgr.model_dict.items():
+            arrays[f"params_{key}"] = net._flat.detach().float().cpu().numpy()
+    assert sum(a.nbytes for a in arrays.values()) <= 64e6
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def spawn_ranks(n: int) -> int:
     """`python bench.py --gpus N` without a launcher: start N ranks of this script (one process per GPU, LOCAL_RANK = device
     index, rendezvous on 127.0.0.1 at a free port) — what `python -m torch.distributed.run --nproc-per-node N` would do.  Rank 0
@@ -234,6 +260,10 @@ def main():
         with torch.cuda.stream(_s):
             torch.zeros(1, device="cuda")
     trainer = cva.RetrievalTrainer(cfg, mgr, is_test=args.eval)
+    # the same arguments compute the same steps: the fp32 atomic sums go through order-independent fixed-point accumulators (with Adam,
+    # their last-bit noise in arrival order would otherwise turn into different parameter trajectories from run to run)
+    deterministic = not args.eval and not args.nondeterministic
+    trainer.set_deterministic(deterministic)
     if dp is not None:
         trainer.dp = dp
         trainer.comm_stream = torch.cuda.Stream()
@@ -258,7 +288,7 @@ def main():
             with torch.no_grad():
                 v = mgr.encode_visual(batch)
                 t = mgr.encode_text(batch)
-            return v.vid_emb.sum() + t.par_emb.sum()
+            return v.vid_emb.sum() + t.par_emb.sum(), v, t
     else:
         mgr.set_all_models_train()
         if args.no_dropout:
@@ -294,10 +324,10 @@ def main():
                     cur, nxt = pair[turn[0] & 1], pair[(turn[0] + 1) & 1]
                     turn[0] += 1
                     return trainer.train_step_native(cur, vid_counts=vid_counts, clip_counts=clip_counts, defer_join=not args.no_defer_join,
-                                                     next_batch=nxt if la_on[0] else None)[0]
+                                                     next_batch=nxt if la_on[0] else None)
                 return trainer.train_step_native(batch, vid_counts=vid_counts, clip_counts=clip_counts, defer_join=not args.no_defer_join,
-                                                 use_graph=(mode == "native-graph"))[0]
-            return trainer.train_step(batch, vid_counts, clip_counts)[0]
+                                                 use_graph=(mode == "native-graph"))
+            return trainer.train_step(batch, vid_counts, clip_counts)
 
     def barrier():
         if dp is not None:
@@ -387,6 +417,10 @@ def main():
     host_issue = time.perf_counter() - t0  # CPU time to enqueue K steps (informational)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, mgr, args.eval)
+    if deterministic and trainer.det_bypass_count() > 0:  # (synchronises: after the timed steps)
+        sys.stderr.write(f"bench.py: {trainer.det_bypass_count()} gradient / loss addends left the fixed-point range: this run is not bit-reproducible\n")
     sysfs_clocks("after the timed steps")
     blocks = [1e3 * elapsed / args.steps]
     for _ in range(args.repeat - 1):  # regime probe: the same bracket again, in the same process
@@ -414,7 +448,7 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         cdist._all_reduce(t, torch.distributed.ReduceOp.MAX)  # (host-staged under gloo)
         elapsed = float(t.item())
-    loss_val = float(last)
+    loss_val = float(last[0])
     loss_words = None
     if not args.eval and getattr(trainer, "_native", None) is not None and getattr(trainer._native, "losses", None) is not None:
         loss_words = [float(v) for v in trainer._native.losses[:3].tolist()]  # (total, contrastive, cycle-consistency) of the last step
@@ -462,7 +496,7 @@ def main():
         sys.stderr.write("  per 1/16 step (GHz, first monitored step): " + " ".join(f"{ghz[20 + i * per:20 + (i + 1) * per].mean():.2f}" for i in range(16)) + "\n")
 
     roofline = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # same steps again with HIP events around every gemm_nt launch (the dominant kernel: all Linear layers,
         # forward and dX).  Kept out of the timed region so `value` carries no instrumentation overhead.
         nst = max(2, min(5, args.steps))
@@ -622,7 +656,7 @@ def main():
                        "parallelism": f"dp{world}", "mode": "eval" if args.eval else "train",
                        **({"collectives": {"direct": "RCCL calls on the step's own streams (dist.DirectRccl)", "torch": "torch.distributed"}[dp.collectives_route()]}
                           if (dp is not None and not args.eval) else {}),
-                       "launch": "eval" if args.eval else mode,
+                       "launch": "eval" if args.eval else mode, **({"deterministic": True} if deterministic else {}),
                        **({"batches": "two different synthetic batches in turn"} if (not args.eval and two_batches) else {}),
                        **({"input_lookahead": "each step runs the NEXT batch's input LayerNorm (one per side per step, as without it) next to its global networks"}
                           if (not args.eval and lookahead and getattr(getattr(trainer, "_native", None), "stages", None) is not None) else {}),
@@ -640,7 +674,7 @@ def main():
         }
         if roofline is not None:
             out["roofline"] = roofline
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(w)
         print(json.dumps(out))
     if dp is not None:

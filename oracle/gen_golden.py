@@ -21,7 +21,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 REF = os.environ.get("COOT_REFERENCE", "/root/reference")
-OUT = os.environ.get("COOT_GOLDEN_OUT", os.path.join(ROOT, "tests", "golden"))  # (tests regenerate into a scratch directory and compare)
+OUT = os.environ.get("COOT_GOLDEN_OUT", os.path.join(ROOT, "tests", "golden"))  # (another directory: regenerate next to the committed fixtures)
 
 # ---- import shims (no reference edits) -------------------------------------------------------
 for _n in ("Iterable", "Mapping", "Sequence", "MutableMapping"):
@@ -842,6 +842,62 @@ def gen_traj_anet_ragged_packed_eps():
                          steps=3, p=0.1, step_seed0=5150201, ragged=True, full=False, packed=True)
 
 
+CONTRASTIVE_FLAG_CASES = [(True, True), (False, False), (True, False)]  # (max_violation, norm)
+
+
+def gen_contrastive_flags():
+    """The reference's ContrastiveLoss (coot/loss_fn.py:51-100) with the two constructor flags no configuration reaches, on fixed
+    normalised embeddings: loss and the gradients wrt both inputs per (max_violation, norm) case (tests/test_reference_binding.py)."""
+    g = th.Generator().manual_seed(3)
+    base = th.randn(1, 48, generator=g)
+    im = F.normalize(base + 0.7 * th.randn(20, 48, generator=g), dim=-1)
+    s = F.normalize(im + 0.4 * th.randn(20, 48, generator=g), dim=-1)
+    out = {"im": im.numpy(), "s": s.numpy()}
+    for mv, norm in CONTRASTIVE_FLAG_CASES:
+        a, b = im.clone().requires_grad_(True), s.clone().requires_grad_(True)
+        loss = ContrastiveLoss(0.2, max_violation=mv, norm=norm, use_cuda=False)(a, b)
+        loss.backward()
+        tag = f"{int(mv)}{int(norm)}"
+        out["loss_" + tag] = np.array(float(loss))
+        out["grad_im_" + tag], out["grad_s_" + tag] = a.grad.numpy(), b.grad.numpy()
+    np.savez_compressed(os.path.join(OUT, "contrastive_flags.npz"), **out)
+    print("wrote contrastive_flags")
+
+
+def _attrs(obj):
+    """A config object of the reference as nested plain values (its attributes; enums by name)."""
+    if isinstance(obj, (str, int, float, bool, type(None))):
+        return obj
+    if isinstance(obj, (list, tuple)):
+        return [_attrs(v) for v in obj]
+    if hasattr(obj, "__dict__"):
+        return {k: _attrs(v) for k, v in vars(obj).items()}
+    return {"name": obj.name}
+
+
+def gen_manager_contract():
+    """What the reference's RetrievalModelManager on its ActivityNet config (four TransformerLegacy networks) exposes to a caller:
+    state-dict entries per network (name, shape, dtype, in order), get_all_params (names, shapes, decay_mult), and the attributes of
+    the TransformerConfig objects it hands each network (tests/test_reference_binding.py)."""
+    import json
+    d = utils_yaml.load_yaml_config_file(os.path.join(REF, "config/retrieval/paper2020/anet_coot.yaml"))
+    d["use_cuda"] = False
+    d["fp16_train"] = False
+    d["fp16_val"] = False
+    cfg = RetrievalConfig(d)
+    th.manual_seed(0)
+    mgr = model_retrieval.RetrievalModelManager(cfg)
+    state = {net: [[k, list(v.shape), str(v.dtype).replace("torch.", "")] for k, v in sd.items()] for net, sd in mgr.get_model_state().items()}
+    params, names, _flat = mgr.get_all_params()
+    out = {"state": state,
+           "all_params": {"names": names, "shapes": [list(p["params"].shape) for p in params], "decay_mult": [p["decay_mult"] for p in params]},
+           "model_cfgs": {net: _attrs(cfg.model_cfgs[net]) for net in state}}
+    with open(os.path.join(OUT, "manager_contract.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print("wrote manager_contract")
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     only = sys.argv[1:]  # e.g. "lr_schedule": regenerate just that fixture
@@ -884,6 +940,8 @@ def main():
     gen_lr_schedule()
     gen_collate()
     gen_mask_semantics()
+    gen_contrastive_flags()
+    gen_manager_contract()
 
 
 if __name__ == "__main__":

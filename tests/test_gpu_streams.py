@@ -22,6 +22,18 @@ def _opt(cva, name):
     return v.value
 
 
+def _overlap(lib, x, y, tries=3):
+    """coot_streams_overlap, measured again when it says 0: two streams on one hardware queue never overlap, so a single 0 next to a
+    1 is a spin kernel that started late (the measurement is timed), while a shared queue gives 0 every time."""
+    for t in range(tries):
+        r = lib.coot_streams_overlap(x, y)
+        if r != 0:
+            if t:
+                print(f"overlap of {x:#x} / {y:#x} seen on measurement {t + 1}")
+            return r
+    return 0
+
+
 def test_overlap_test_sees_shared_queues(env):
     """The hazard is real and the test sees it: among nine streams taken from torch's pool at least two share one of the 4 hardware
     queues (their spin kernels run one after the other), and a stream never overlaps itself."""
@@ -57,7 +69,7 @@ def test_created_streams_overlap_whatever_was_created_before(env, before):
         hs = [main.cuda_stream, a.cuda_stream, b.cuda_stream, c.cuda_stream]
         for i in range(4):
             for j in range(i + 1, 4):
-                assert lib.coot_streams_overlap(hs[i], hs[j]) == 1, (i, j)
+                assert _overlap(lib, hs[i], hs[j]) == 1, (i, j)
         with torch.cuda.stream(a.torch):  # usable from torch
             x = torch.ones(8, device="cuda") * 2
         torch.cuda.synchronize()
@@ -93,7 +105,7 @@ def test_step_streams_are_concurrent_in_every_creation_order(env, before):
     torch.cuda.synchronize()
     st = tr._native
     assert st.text_cs.concurrent
-    assert lib.coot_streams_overlap(torch.cuda.current_stream().cuda_stream, st.streams[1].cuda_stream) == 1
+    assert _overlap(lib, torch.cuda.current_stream().cuda_stream, st.streams[1].cuda_stream) == 1
     assert _opt(cva, "stream_unresolved") == unresolved0
     val = float(losses[0])
     assert val == val and val > 0
@@ -103,7 +115,7 @@ def test_step_streams_are_concurrent_in_every_creation_order(env, before):
     with torch.cuda.stream(other):
         l2 = tr.train_step_native(batch, do_optimizer=False)
         torch.cuda.synchronize()
-        assert lib.coot_streams_overlap(other.cuda_stream, tr._native.streams[1].cuda_stream) == 1
+        assert _overlap(lib, other.cuda_stream, tr._native.streams[1].cuda_stream) == 1
     assert abs(float(l2[0]) - val) <= 1e-6 * max(1.0, abs(val))
     tr.close()
 

@@ -1,52 +1,52 @@
-"""The drop-in boundary, exercised from the REFERENCE's side: the reference's own
-RetrievalModelManager with the one added dispatch branch (coot_videotext_amd.integration.reference_manager_class) builds the HIP
-networks from the reference's TransformerConfig objects, loads the state of the reference's TransformerLegacy networks strictly,
-and keeps the BaseModelManager contract (get_all_params names and decay_mult, get / set_model_state incl. the legacy renames).
+"""The drop-in boundary against what the reference's own RetrievalModelManager exposes, as
+recorded from it by oracle/gen_golden.py (tests/golden/manager_contract.json: state-dict entries, get_all_params, the TransformerConfig
+objects it hands each network): the HIP networks load the reference's state strictly and keep the BaseModelManager contract
+(get_all_params names and decay_mult, get / set_model_state incl. the legacy renames), and the config adapter of
+coot_videotext_amd.integration maps the reference's config objects to the kernels' fields.  The two constructor flags of the
+reference's ContrastiveLoss that no configuration reaches are pinned by tests/golden/contrastive_flags.npz.
 
-Container-only: needs /root/reference (skipped on the GPU box).  No GPU: the parameter layout is host code of the library."""
+No GPU: the parameter layout is host code of the library."""
 import copy
+import json
 import os
+import types
 
 import numpy as np
 import pytest
 
-from tests import helpers as H
 
-REF = H.import_reference()
-pytestmark = pytest.mark.skipif(REF is None, reason="the reference tree is not present (GPU box)")
-
-
-def _ref_cfg(hip: bool):
-    d = REF.utils_yaml.load_yaml_config_file(os.path.join(REF.root, "config/retrieval/paper2020/anet_coot.yaml"))
-    d["use_cuda"] = False
-    d["fp16_train"] = False
-    d["fp16_val"] = False
-    if hip:  # what `-o net_video_local.name=transformer_hip,...` does; the other three inherit through same_as or are set here
-        for k in ("net_video_local", "net_video_global", "net_text_local", "net_text_global"):
-            d[k]["name"] = "transformer_hip"
-    return REF.configs_retrieval.RetrievalConfig(d)
+def _namespace(d):
+    """A recorded config object (nested attribute dicts) back as an object with those attributes."""
+    if isinstance(d, dict):
+        return types.SimpleNamespace(**{k: _namespace(v) for k, v in d.items()})
+    return d
 
 
-def test_reference_manager_builds_hip_networks_and_keeps_the_manager_contract():
+def test_hip_manager_keeps_the_reference_manager_contract(golden_dir):
     import torch
+    import coot_videotext_amd as cva
     from coot_videotext_amd import integration
     from coot_videotext_amd.nets import TransformerHip
+    with open(os.path.join(golden_dir, "manager_contract.json")) as f:
+        rec = json.load(f)
     torch.manual_seed(0)
-    ref_mgr = REF.model_retrieval.RetrievalModelManager(_ref_cfg(False))       # four TransformerLegacy networks
-    HipMgr = integration.reference_manager_class()
-    assert issubclass(HipMgr, REF.model_retrieval.RetrievalModelManager)
-    hip_mgr = HipMgr(_ref_cfg(True))
-    assert list(hip_mgr.model_dict) == list(ref_mgr.model_dict)
+    hip_mgr = cva.RetrievalModelManager(cva.load_named_config("anet_coot"))
+    assert list(hip_mgr.model_dict) == list(rec["state"])
     assert all(isinstance(m, TransformerHip) for m in hip_mgr.model_dict.values())
     # the adapter: the reference's config OBJECT (transformer_legacy.py:26-97) -> the fields the kernels take
-    c = integration.hip_config_from_reference(_ref_cfg(True).model_cfgs["net_video_global"], 384)
+    ref_cfgs = {net: _namespace(c) for net, c in rec["model_cfgs"].items()}
+    for c in ref_cfgs.values():  # what `-o net_video_local.name=transformer_hip,...` does
+        c.name = integration.HIP_NAME
+    c = integration.hip_config_from_reference(ref_cfgs["net_video_global"], 384)
     assert (c.hidden_dim, c.num_heads, c.ff_dim, c.use_context, c.use_input_fc, c.pooler, c.dropout, c.ctx_dropout) == \
         (384, 8, 384, True, False, "avg_special", 0.025, 0.025)
-    c = integration.hip_config_from_reference(_ref_cfg(True).model_cfgs["net_text_local"], 1536)
+    c = integration.hip_config_from_reference(ref_cfgs["net_text_local"], 1536)
     assert (c.input_dim, c.pooler, c.pool_hidden, c.pool_heads, c.pool_dropout) == (1536, "atn", 768, 2, 0.025)
 
-    # 1. state dicts: same keys and shapes; the reference's state loads STRICTLY (load_state_dict default) and round-trips
-    state = ref_mgr.get_model_state()
+    # 1. state dicts: a state with the reference's entries and shapes loads STRICTLY (load_state_dict default) and round-trips
+    g = torch.Generator().manual_seed(1)
+    state = {net: {k: (torch.randn(shape, generator=g) if dt == "float32" else torch.zeros(shape, dtype=getattr(torch, dt)))
+                   for k, shape, dt in entries} for net, entries in rec["state"].items()}
     assert not hip_mgr.was_loaded
     hip_mgr.set_model_state(copy.deepcopy(state))
     assert hip_mgr.was_loaded
@@ -75,12 +75,23 @@ def test_reference_manager_builds_hip_networks_and_keeps_the_manager_contract():
         for k, v in hip_mgr.model_dict[net].state_dict().items():
             assert torch.equal(v.cpu(), state[net][k] + 1.0), (net, k)
 
-    # 3. optimizer-facing contract: names, count and decay_mult of get_all_params (bias decay_mult 0: weight_decay_for_bias)
-    p_ref, n_ref, f_ref = ref_mgr.get_all_params()
+    # 3. optimizer-facing contract.  The reference's get_all_params (get_params_opt_simple) lists EVERY named parameter of the four
+    #    networks — 118, the two requires_grad=False pooler.pools.0.genpool_one included — with decay_mult 0 for biases
+    #    (weight_decay_for_bias); the drop-in route (integration.reference_manager_class) inherits that method, so over the HIP networks
+    #    it returns exactly this list: names, count, shapes, order and decay_mult are checked in full.  This package's own manager
+    #    differs from the reference on purpose (model_retrieval.py: get_all_params): it leaves the non-trainable parameters out (116),
+    #    so its list is the trainable subset of the reference's, with the reference's decay_mult.
+    ref = rec["all_params"]
+    named = [(k, v) for m in hip_mgr.model_dict.values() for k, v in m.named_parameters()]
+    assert [k for k, _ in named] == ref["names"] and len(named) == len(ref["shapes"]) == 118
+    assert [list(v.shape) for _, v in named] == ref["shapes"]
+    wd_bias = hip_mgr.cfg.optimizer.weight_decay_for_bias
+    assert [0.0 if (wd_bias and "bias" in k) else 1.0 for k, _ in named] == ref["decay_mult"]
+    trainable = [i for i, (_, v) in enumerate(named) if v.requires_grad]
+    assert len(trainable) == 116 and all("genpool_one" in ref["names"][i] for i in range(118) if i not in trainable)
     p_hip, n_hip, f_hip = hip_mgr.get_all_params()
-    assert n_hip == n_ref and len(f_hip) == len(f_ref) == 118
-    assert [p["decay_mult"] for p in p_hip] == [p["decay_mult"] for p in p_ref]
-    assert [tuple(p["params"].shape) for p in p_hip] == [tuple(p["params"].shape) for p in p_ref]
+    assert n_hip == [ref["names"][i] for i in trainable]
+    assert [p["decay_mult"] for p in p_hip] == [ref["decay_mult"][i] for i in trainable]
     assert sum(int(np.prod(t.shape)) for t in f_hip if t.requires_grad) == 7604224
     # 4. train / eval switches reach the networks
     hip_mgr.set_all_models_eval()
@@ -111,24 +122,19 @@ def test_own_manager_loads_legacy_list_checkpoints():
 
 
 @pytest.mark.parametrize("max_violation,norm", [(True, True), (False, False), (True, False)])
-def test_contrastive_loss_constructor_flags_match_the_reference_module(max_violation, norm):
+def test_contrastive_loss_constructor_flags_match_the_reference_module(golden_dir, max_violation, norm):
     """ContrastiveLoss(margin, max_violation, norm) (coot/loss_fn.py:51-100): the two constructor flags no configuration reaches — the
     hardest negative per query only, the un-normalised sum — against the reference's module on the same normalised embeddings: loss and
-    gradients wrt both inputs.  (The default flags are the fused HIP loss, pinned on the GPU by test_losses_vs_oracle and the fixtures.)"""
+    gradients wrt both inputs (tests/golden/contrastive_flags.npz).  (The default flags are the fused HIP loss, pinned on the GPU by
+    test_losses_vs_oracle and the fixtures.)"""
     import torch
     import coot_videotext_amd as cva
-    from coot import loss_fn as ref_loss
-    g = torch.Generator().manual_seed(3)
-    base = torch.randn(1, 48, generator=g)
-    im = torch.nn.functional.normalize(base + 0.7 * torch.randn(20, 48, generator=g), dim=-1)
-    s = torch.nn.functional.normalize(im + 0.4 * torch.randn(20, 48, generator=g), dim=-1)
-    outs = []
-    for mod in (ref_loss.ContrastiveLoss(0.2, max_violation=max_violation, norm=norm, use_cuda=False),
-                cva.ContrastiveLoss(0.2, max_violation=max_violation, norm=norm, use_cuda=False)):
-        a, b = im.clone().requires_grad_(True), s.clone().requires_grad_(True)
-        loss = mod(a, b)
-        loss.backward()
-        outs.append((float(loss), a.grad.clone(), b.grad.clone()))
-    (lr, gar, gbr), (lo, gao, gbo) = outs
+    fx = np.load(os.path.join(golden_dir, "contrastive_flags.npz"))
+    tag = f"{int(max_violation)}{int(norm)}"
+    lr, gar, gbr = float(fx["loss_" + tag]), torch.from_numpy(fx["grad_im_" + tag]), torch.from_numpy(fx["grad_s_" + tag])
+    a, b = torch.from_numpy(fx["im"]).requires_grad_(True), torch.from_numpy(fx["s"]).requires_grad_(True)
+    loss = cva.ContrastiveLoss(0.2, max_violation=max_violation, norm=norm, use_cuda=False)(a, b)
+    loss.backward()
+    lo, gao, gbo = float(loss), a.grad, b.grad
     assert lr > 0 and abs(lr - lo) <= 1e-6 * abs(lr)
     assert torch.allclose(gar, gao, rtol=1e-5, atol=1e-7) and torch.allclose(gbr, gbo, rtol=1e-5, atol=1e-7)

@@ -1,7 +1,7 @@
 set -u
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out/r04
-B="python bench.py --steps 200 --warmup 20"
+B="python bench.py --full --steps 200 --warmup 20"
 $B > gpurun_out/r04/bench_train_anet.json 2> gpurun_out/r04/bench_train_anet.err
 $B --workload yc2_100m > gpurun_out/r04/bench_yc2_100m.json 2> gpurun_out/r04/bench_yc2_100m.err
 for w in yc2_2d3d yc2_2d3d_2816 hbm_stress anet_ragged; do $B --workload $w --no-cpu-baseline > gpurun_out/r04/bench_$w.json 2> gpurun_out/r04/bench_$w.err; done

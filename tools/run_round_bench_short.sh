@@ -3,7 +3,7 @@ set -u
 cd $GRAFT_REPO_ROOT
 TAG=${1:-r04b}
 mkdir -p gpurun_out/$TAG
-B="python bench.py --steps 200 --warmup 20"
+B="python bench.py --full --steps 200 --warmup 20"
 $B > gpurun_out/$TAG/bench_train_anet.json 2> gpurun_out/$TAG/bench_train_anet.err
 for w in yc2_100m yc2_2d3d anet_ragged hbm_stress; do $B --workload $w --no-cpu-baseline > gpurun_out/$TAG/bench_$w.json 2> /dev/null; done
 $B --eval --no-cpu-baseline > gpurun_out/$TAG/bench_eval_anet.json 2> /dev/null
