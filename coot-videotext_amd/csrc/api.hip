@@ -662,6 +662,8 @@ int coot_debug_attn_dropout_scales(uint64_t seed, unsigned site, unsigned row32,
 int coot_debug_timestamps(void* dev_u64) { g_fz_tstamps = (unsigned long long*)dev_u64; return 0; }
 extern "C" void coot_step_stamps_enable(int on);  // api_step.hip
 extern "C" void coot_step_grad_write(int on);
+extern "C" void coot_step_det_seg_flush(int on);
+extern "C" int coot_step_det_seg_flush_get(void);
 extern "C" int coot_internal_stage_hits(void);
 extern "C" int coot_internal_stream_counter(int which);  // api_step.hip: StreamPicker
 extern "C++" { namespace coot { int det_bypass_count(); } }  // det.hip
@@ -678,6 +680,7 @@ int coot_get_option(const char* name, int* value) {
   if (!strcmp(name, "stream_candidates_rejected")) { *value = coot_internal_stream_counter(1); return 0; }
   if (!strcmp(name, "stream_unresolved")) { *value = coot_internal_stream_counter(2); return 0; }
   if (!strcmp(name, "operand_f16")) { *value = COOT_OPERAND_IS_F16; return 0; }  // which build this is (common.h)
+  if (!strcmp(name, "det_seg_flush")) { *value = coot_step_det_seg_flush_get(); return 0; }
   if (!strcmp(name, "det_bypasses")) { *value = det_bypass_count(); return 0; }  // deterministic mode: addends that took the float atomic (synchronises; -1: mode off)
   set_error("get_option: unknown or write-only option %s", name);
   return -2;
@@ -698,6 +701,7 @@ int coot_set_option(const char* name, int value) {
   if (!strcmp(name, "tn_target_wgs")) { set_tn_target_wgs(value); return 0; }
   if (!strcmp(name, "xcd_order")) { set_xcd_order(value); return 0; }
   if (!strcmp(name, "grad_write")) { coot_step_grad_write(value); return 0; }
+  if (!strcmp(name, "det_seg_flush")) { coot_step_det_seg_flush(value); return 0; }  // 0: deterministic steps flush whole arenas in launches of their own
   if (!strcmp(name, "glob_flush_aux")) { g_glob_flush_aux = value; return 0; }
   if (!strcmp(name, "pool_handover")) { g_pool_handover_on = value; return 0; }  // 0: the pack between the local and the global forward stays a launch of its own  // 0: the global network's weight-gradient launch stays on its side's stream
   if (!strcmp(name, "cl_col_split")) { set_cl_col_split(value); return 0; }
@@ -926,6 +930,7 @@ size_t coot_net_scratch_bytes(const coot_net_config* cfg, int N, int Lseq, int N
 // accumulated (biases, LayerNorm parameters: < 1 % of the arena) — one launch instead of four fills.
 static thread_local int g_grad_overwrite = 0;
 int coot_net_grads_overwrite(int on) { g_grad_overwrite = on ? 1 : 0; return 0; }
+extern "C" int coot_internal_grads_overwrite(void) { return g_grad_overwrite; }
 
 struct ZeroRanges { float* p[64]; int n[64]; int poison[64]; int count; };
 __global__ __launch_bounds__(256) void zero_ranges_kernel(ZeroRanges r) {
@@ -943,6 +948,29 @@ static void written_matrices(const coot_net_config& c, const NetLayout& L, std::
   for (const LayerP& lp : L.ctx) layer(lp);
   if (c.pooler == 0) { mats.push_back({L.pw1, D * (int64_t)c.pool_hidden}); mats.push_back({L.pw2, (int64_t)c.pool_hidden * (D / c.pool_heads)}); }
   std::sort(mats.begin(), mats.end());
+}
+// the complement: what a backward pass in overwrite mode still ACCUMULATES into (biases, LayerNorm parameters), as (offset, elements) in
+// ascending order — the ranges coot_nets_zero_grads(skip_matrices = 1) zeroes and the deterministic step flushes (api_step.hip)
+static int accumulated_ranges(const coot_net_config& c, const NetLayout& L, std::vector<std::pair<int64_t, int64_t>>& acc,
+                              std::vector<std::pair<int64_t, int64_t>>* mats_out = nullptr) {
+  std::vector<std::pair<int64_t, int64_t>> mats; written_matrices(c, L, mats);
+  int64_t pos = 0;
+  for (const auto& m : mats) {
+    COOT_REQUIRE(m.first >= pos && m.first + m.second <= L.total, "gradient arena: parameter layout");
+    if (m.first > pos) acc.push_back({pos, m.first - pos});
+    pos = m.first + m.second;
+  }
+  if (L.total > pos) acc.push_back({pos, L.total - pos});
+  if (mats_out) *mats_out = mats;
+  return 0;
+}
+extern "C" int coot_internal_grad_accum_ranges(const coot_net_config* cfg, int64_t* offsets, int64_t* sizes, int max_ranges) {
+  coot_net_config c; RUN(norm_cfg(cfg, &c));
+  NetLayout L; build_layout(c, L);
+  std::vector<std::pair<int64_t, int64_t>> acc; RUN(accumulated_ranges(c, L, acc));
+  COOT_REQUIRE((int)acc.size() <= max_ranges, "grad_accum_ranges: %d ranges (room for %d)", (int)acc.size(), max_ranges);
+  for (size_t i = 0; i < acc.size(); ++i) { offsets[i] = acc[i].first; sizes[i] = acc[i].second; }
+  return (int)acc.size();
 }
 // host-only (tests): the ranges coot_nets_zero_grads(skip_matrices = 1) leaves alone; returns their number (or -1)
 int coot_debug_written_matrices(const coot_net_config* cfg, int64_t* offsets, int64_t* sizes, int max_ranges) {
@@ -982,16 +1010,11 @@ int coot_nets_zero_grads_ex(int nnets, const coot_net_config* const* cfgs, float
     coot_net_config c; RUN(norm_cfg(cfgs[k], &c));
     NetLayout L; build_layout(c, L);
     if (!skip_matrices) { RUN(check_hip(hipMemsetAsync(grads[k], 0, (size_t)L.total * sizeof(float), st), "memset grads")); continue; }
-    // the matrices a backward pass writes (offset, elements), ascending offsets; everything between them is zeroed
-    std::vector<std::pair<int64_t, int64_t>> mats; written_matrices(c, L, mats);
-    int64_t pos = 0;
-    for (const auto& m : mats) {
-      COOT_REQUIRE(m.first >= pos && m.first + m.second <= L.total, "nets_zero_grads: parameter layout");
-      RUN(add(grads[k] + pos, m.first - pos, 0));
-      if (g_grad_poison) RUN(add(grads[k] + m.first, m.second, 1));
-      pos = m.first + m.second;
-    }
-    RUN(add(grads[k] + pos, L.total - pos, 0));
+    // everything between the matrices a backward pass writes is zeroed (the poison test fills the matrices with NaN)
+    std::vector<std::pair<int64_t, int64_t>> acc, mats; RUN(accumulated_ranges(c, L, acc, &mats));
+    for (const auto& a : acc) RUN(add(grads[k] + a.first, a.second, 0));
+    if (g_grad_poison)
+      for (const auto& m : mats) RUN(add(grads[k] + m.first, m.second, 1));
   }
   for (int e = 0; e < n_extra; ++e)
     for (int64_t o = 0; o < extra_n[e]; o += (1 << 30)) RUN(add(extra[e] + o, extra_n[e] - o < (1 << 30) ? extra_n[e] - o : (1 << 30), 0));

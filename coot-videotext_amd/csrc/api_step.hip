@@ -148,6 +148,35 @@ struct EarlyUpdate { bool on[2] = {false, false}; const coot_step_config* cfg = 
 thread_local EarlyUpdate g_early;
 int early_update_fire(int side, int gi, hipStream_t st);  // below (needs adam_nets)
 int g_grad_write = 1;  // coot_set_option("grad_write", 0/1): coot_train_step writes the weight-matrix gradients and zeroes only the rest
+
+// Deterministic mode (det.h) without flushes of its own on the sides' tails (coot_set_option("det_seg_flush", 0/1), default 1).
+// A backward pass in overwrite mode WRITES every weight-matrix gradient with a plain store, so of a gradient arena only the words
+// between those matrices (biases, LayerNorm parameters: coot_nets_zero_grads' ranges) can hold a fixed-point sum: they alone are
+// flushed — by the update launch that reads them where the step updates (adam4_kernel; the loss words by its rider), else by one
+// segment launch per side.  An arena whose matrices were accumulated into (grads_overwrite off, or launch_gemm_tn's one-pass path:
+// det_take_matrix_atomics) is flushed whole.  The global networks' early update then runs in this mode too.  0: the full-arena
+// flush launches at the end of each side's backward and in front of the video side's update, no early update (rounds 4-6).
+extern "C" int coot_internal_grad_accum_ranges(const coot_net_config* cfg, int64_t* offsets, int64_t* sizes, int max_ranges);  // api.hip
+extern "C" int coot_internal_grads_overwrite(void);                                                                         // api.hip
+int g_det_seg = 1;
+struct DetPlan {
+  bool fold = false;                          // the step's update launches flush the arenas they read (and the loss words)
+  bool full[4] = {true, true, true, true};    // flush this arena whole (set behind its backward pass)
+  float* losses = nullptr;                    // the step's three loss words (flushed with the video side's arenas)
+};
+thread_local DetPlan g_det_plan;
+// the words of gradient arena `net` that can hold a fixed-point sum -> `out` (no-op while the mode is off)
+int det_arena_segs(const coot_step_config& c, const coot_step_buffers& b, int net, DetSegs& out, hipStream_t st) {
+  const long n = (long)coot_net_param_numel(&c.net[net]);
+  if (g_det_plan.full[net]) return det_segs_add(out, b.grads[net], n, st);
+  int64_t off[64], len[64];
+  const int k = coot_internal_grad_accum_ranges(&c.net[net], off, len, 64);
+  if (k < 0) return k;
+  for (int i = 0; i < k; ++i) RUN(det_segs_add(out, b.grads[net] + off[i], (long)len[i], st));
+  return 0;
+}
+// after the backward pass of arena `net`: whole or segments (see g_det_seg)
+void det_plan_arena(int net) { g_det_plan.full[net] = !coot_internal_grads_overwrite() || det_take_matrix_atomics(); }
 // bf16 weight packs of `count` networks in one launch
 int pack_nets(const coot_step_config& c, const coot_step_buffers& b, const int* nets, int count, void* stream) {
   const coot_net_config* cfgs[4]; const float* Ps[4]; void* ws[4];
@@ -409,17 +438,26 @@ int side_backward(const coot_step_config& c, const coot_step_buffers& b, int li,
   glob_xcd_set(side == 0 ? 0 : 4, 4);
   // with an early update the global network's weight gradients are consumed on the library's own stream: their launch goes there too
   if (g_early.on[side] && g_pipe.init() == 0) coot_internal_set_glob_flush_stream(g_pipe.stream);
+  (void)det_take_matrix_atomics();
   const int rc_g = coot_net_bwd(&c.net[gi], b.params[gi], b.wpack[gi], b.pe[gi], resh, item_num, d.B, Cmax, nullptr, nullptr, 0, 0, local_out, d_glob,
                                 b.grads[gi], dhid, dfeat, saved_g, sz_g, (char*)scratch + sz_loc, sz_glob, train, seed + 11 * gi, g_step_seed_dev, st,
                                 nullptr);
   glob_xcd_set(0, 8);
   coot_internal_set_glob_flush_stream(nullptr);
   RUN(rc_g);
+  det_plan_arena(gi);
   g_stamps.mark(li == 0 ? "video: global backward done" : "text: global backward done", st);
   // data parallel: the global network's gradients are final here — the caller's communication stream may start reducing them under
   // the local backward (coot_step_set_global_done_events)
+  const bool seg = det_on() && g_det_seg;
   if (g_glob_done[side]) {
-    if (det_on()) RUN(det_flush_range(b.grads[gi], (size_t)coot_net_param_numel(&c.net[gi]) * sizeof(float), st));  // (their fixed-point sums first)
+    if (seg) {  // (their fixed-point sums first)
+      DetSegs ds;
+      RUN(det_arena_segs(c, b, gi, ds, st));
+      RUN(det_flush_segs(ds, st));
+    } else if (det_on()) {
+      RUN(det_flush_range(b.grads[gi], (size_t)coot_net_param_numel(&c.net[gi]) * sizeof(float), st));
+    }
     RUN(check_hip(hipEventRecord((hipEvent_t)g_glob_done[side], st), "eventRecord"));
   }
   if (g_early.on[side]) RUN(early_update_fire(side, gi, st));
@@ -428,12 +466,22 @@ int side_backward(const coot_step_config& c, const coot_step_buffers& b, int li,
   if (g_resh_wait_slot >= 0 && li == 0) RUN(g_hops.wait(g_resh_wait_slot, st));
   // context grad += dhidden, item grads += unpack(global input grad) + unpack(cycle-consistency grad): one launch
   RUN(launch_pack_bwd_join(dfeat, d_resh, dhid, (const long long*)item_num, d.B, Cmax, D, d_local + (size_t)d.B * D, d_local, st));
+  (void)det_take_matrix_atomics();
   const int rc = coot_net_bwd(&c.net[li], b.params[li], b.wpack[li], b.pe[li], ctx_feat, ctx_len, d.B, Lctx, item_feat, item_len, d.Nc, Litem,
                               nullptr, d_local, b.grads[li], nullptr, nullptr, saved_l, sz_l, scratch, sz_loc, train, seed + 11 * li, g_step_seed_dev,
                               st, pk);
   RUN(rc);
-  // deterministic mode (det.h): this side's fixed-point sums -> its two gradient arenas, behind everything that added to them
-  if (det_on()) {
+  det_plan_arena(li);
+  // deterministic mode (det.h): this side's fixed-point sums -> its two gradient arenas, behind everything that added to them.  With
+  // g_det_seg: nothing here when the step's update launches flush them (g_det_plan.fold), else their segments (+ the loss words on the
+  // video side) in one launch; the global arena only if no one flushed it above
+  if (seg && !g_det_plan.fold) {
+    DetSegs ds;
+    RUN(det_arena_segs(c, b, li, ds, st));
+    if (!g_glob_done[side]) RUN(det_arena_segs(c, b, gi, ds, st));
+    if (side == 0 && g_det_plan.losses) RUN(det_segs_add(ds, g_det_plan.losses, 3, st));
+    RUN(det_flush_segs(ds, st));
+  } else if (det_on() && !seg) {
     RUN(det_flush_range(b.grads[li], (size_t)coot_net_param_numel(&c.net[li]) * sizeof(float), st));
     RUN(det_flush_range(b.grads[gi], (size_t)coot_net_param_numel(&c.net[gi]) * sizeof(float), st));
   }
@@ -500,18 +548,46 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, flo
   for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (long)gridDim.x * 1024) opt_update_range(k, p, g, m, v, decay, i, n);
 }
 
-struct AdamSegs { float* p[4]; const float* g[4]; float* m[4]; float* v[4]; const float* decay[4]; const unsigned char* all1[4]; long n[4]; int blk0[5]; float* losses; };
+// deterministic mode (g_det_seg, det.h): the launch flushes what it reads first — of arena s the words of segments [fseg0[s], fseg0[s + 1])
+// of (flo, fhi) (element offsets) into g[s] from the shadow sh[s] (null: nothing to flush), the three loss words from loss_sh
+constexpr int kAdamFlushSegs = 64;
+struct AdamSegs {
+  float* p[4]; float* g[4]; float* m[4]; float* v[4]; const float* decay[4]; const unsigned char* all1[4]; long n[4]; int blk0[5]; float* losses;
+  long long* sh[4]; long long* loss_sh; int fseg0[5]; int flo[kAdamFlushSegs], fhi[kAdamFlushSegs];
+};
 __global__ __launch_bounds__(256) void adam4_kernel(AdamSegs sg, OptK k_arg, const OptK* k_dev) {
   const OptK k = k_dev ? *k_dev : k_arg;
   int s = 0;
 #pragma unroll
   for (int t = 1; t < 4; ++t) if ((int)blockIdx.x >= sg.blk0[t]) s = t;
   // rider: total = contrastive + cycle-consistency (both final long before any update; was a 1-thread launch in front of the text backward)
-  if (sg.losses && blockIdx.x == 0 && threadIdx.x == 0) sg.losses[0] = sg.losses[1] + sg.losses[2];
+  if (sg.losses && blockIdx.x == 0 && threadIdx.x == 0) {
+    if (sg.loss_sh)
+      for (int w = 0; w < 3; ++w) {
+        const long long v = sg.loss_sh[w];
+        if (v != 0) { sg.loss_sh[w] = 0; sg.losses[w] = det_fold(sg.losses[w], v); }
+      }
+    sg.losses[0] = sg.losses[1] + sg.losses[2];
+  }
   const long n = sg.n[s];
   const int blk = (int)blockIdx.x - sg.blk0[s];
   const long i = ((long)blk * 256 + threadIdx.x) * 4;
   if (i >= n) return;
+  if (long long* sh = sg.sh[s]) {  // (segments are disjoint: a word is flushed once; a workgroup covers 1 024 words)
+    const long b0 = (long)blk * 1024, b1 = b0 + 1024;
+    float* g = sg.g[s];
+    for (int q = sg.fseg0[s]; q < sg.fseg0[s + 1]; ++q) {
+      const long lo = sg.flo[q], hi = sg.fhi[q];
+      if (lo >= b1 || hi <= b0) continue;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const long e = i + j;
+        if (e < lo || e >= hi || e >= n) continue;
+        const long long v = sh[e];
+        if (v != 0) { sh[e] = 0; g[e] = det_fold(g[e], v); }
+      }
+    }
+  }
   // a workgroup = 1 024 consecutive elements: where the caller marked the decay multiplier as 1.0 on all of them (everything but
   // the blocks that touch a bias vector) the mask is not read (coot_step_buffers.decay_block_all)
   const float* decay = (sg.all1[s] && sg.all1[s][blk]) ? nullptr : sg.decay[s];
@@ -554,11 +630,20 @@ __global__ void step_state_kernel(StepState* s, int optimizer, int degen, float 
 }
 
 // Adam update of `count` parameter arenas in ONE launch (four dependent 13 us launches used to end the step)
+// flush: deterministic mode with g_det_seg — the launch first flushes the fixed-point sums of the arenas it reads (g_det_plan) and of
+// the loss words (a segment list that does not fit, or an arena that straddles a registered range: a flush launch of its own in front)
 int adam_nets(const coot_step_config& cfg, const coot_step_buffers& b, const int* nets, int count, int64_t step, hipStream_t st,
-              float* losses = nullptr) {
+              float* losses = nullptr, bool flush = false) {
   AdamSegs sg;
   sg.losses = losses;
-  int blk = 0;
+  sg.loss_sh = nullptr;
+  flush = flush && det_on();
+  DetSegs spill;
+  if (flush && losses) {
+    const int where = det_locate(losses, 3 * sizeof(float), &sg.loss_sh);
+    if (where < 0) RUN(det_segs_add(spill, losses, 3, st));
+  }
+  int blk = 0, nseg = 0;
   for (int k = 0; k < 4; ++k) {
     const int i = nets[k < count ? k : count - 1];
     const long n = k < count ? (long)coot_net_param_numel(&cfg.net[i]) : 0;
@@ -566,8 +651,24 @@ int adam_nets(const coot_step_config& cfg, const coot_step_buffers& b, const int
     sg.all1[k] = b.decay_mask[i] ? b.decay_block_all[i] : nullptr;
     sg.blk0[k] = blk;
     blk += (int)((n / 4 + 255) / 256);
+    sg.sh[k] = nullptr; sg.fseg0[k] = nseg;
+    if (!flush || k >= count) continue;
+    DetSegs ds;
+    RUN(det_arena_segs(cfg, b, i, ds, st));
+    if (ds.n == 0) continue;
+    bool fits = nseg + ds.n <= kAdamFlushSegs && n <= (1L << 30);
+    for (int q = 0; q < ds.n && fits; ++q) fits = ds.s[q].shadow - (ds.s[q].p - b.grads[i]) == ds.s[0].shadow - (ds.s[0].p - b.grads[i]);
+    if (!fits) {  // (one registered range holds the whole arena in every caller: this is the general case's fallback)
+      for (int q = 0; q < ds.n; ++q) RUN(det_segs_add(spill, ds.s[q].p, ds.s[q].n, st));
+      continue;
+    }
+    sg.sh[k] = ds.s[0].shadow - (ds.s[0].p - b.grads[i]);
+    for (int q = 0; q < ds.n; ++q) {
+      sg.flo[nseg] = (int)(ds.s[q].p - b.grads[i]); sg.fhi[nseg] = sg.flo[nseg] + ds.s[q].n; ++nseg;
+    }
   }
-  sg.blk0[4] = blk;
+  sg.blk0[4] = blk; sg.fseg0[4] = nseg;
+  RUN(det_flush_segs(spill, st));
   const OptK k = opt_scalars(cfg.optimizer, cfg.radam_degentosgd, cfg.lr, cfg.beta1, cfg.beta2, cfg.eps, cfg.weight_decay, step);
   hipLaunchKernelGGL(adam4_kernel, dim3(blk), dim3(256), 0, st, sg, k, g_state_dev ? (const OptK*)&g_state_dev->k : (const OptK*)nullptr);
   COOT_CHECK_LAUNCH("adam4");
@@ -591,7 +692,7 @@ int early_update_fire(int side, int gi, hipStream_t st) {
   RUN(g_pipe.init());
   RUN(g_hops.hop(11 + side, st, g_pipe.stream));
   const int nets[1] = {gi};
-  RUN(adam_nets(*g_early.cfg, *g_early.b, nets, 1, g_early.step, g_pipe.stream));
+  RUN(adam_nets(*g_early.cfg, *g_early.b, nets, 1, g_early.step, g_pipe.stream, nullptr, g_det_plan.fold));
   if (g_early.repack) RUN(pack_nets(*g_early.cfg, *g_early.b, nets, 1, g_pipe.stream));
   return g_hops.record(13 + side, g_pipe.stream);
 }
@@ -838,8 +939,11 @@ int coot_train_step(const coot_step_config* cfg, const coot_step_buffers* b, con
   // what the text stream produced for the video side's backward (the cycle-consistency gradient d_resh_v, the local contrastive
   // terms' gradients d_local_v) was recorded in slot 7; side_backward waits where it is first read
   g_resh_wait_slot = 7;
-  // (not in deterministic mode: the fixed-point sums of an arena are flushed at the end of its side's backward; not in a captured step)
-  const bool early = optimize && !det_on() && !g_state_dev;
+  // (in deterministic mode only with g_det_seg: the early update flushes its arena, else the side's backward does at its end; not in a
+  // captured step)
+  struct DetScope { ~DetScope() { g_det_plan = DetPlan{}; } } det_scope;
+  g_det_plan.fold = optimize && g_det_seg; g_det_plan.losses = losses;
+  const bool early = optimize && (!det_on() || g_det_seg) && !g_state_dev;
   const bool early_v = early && (long)d->B * d->Lv + (long)d->Nc * d->Lc >= kEarlyMinTokens;
   const bool early_t = early && (long)d->B * d->Lp + (long)d->Nc * d->Ls >= kEarlyMinTokens;
   struct EarlyScope { ~EarlyScope() { g_early = EarlyUpdate{}; } } early_scope;
@@ -855,8 +959,9 @@ int coot_train_step(const coot_step_config* cfg, const coot_step_buffers* b, con
   // total = contrastive + cycle-consistency rides on the VIDEO side's update launch: both words are final on this stream (its backward
   // waited for the text stream's loss terms, slot 7), and with COOT_STEP_DEFER_TEXT_JOIN the caller's stream is ordered after the video
   // side only — all three loss words are readable there on return (on the text side's launch, losses[0] raced with a deferred join)
-  if (det_on()) RUN(det_flush_range(losses, 3 * sizeof(float), sv));  // (the cycle-consistency word: 2 B addends, det.h)
-  if (optimize) RUN(adam_nets(*cfg, *b, vnets, early_v ? 1 : 2, step, sv, losses));  // (early: the global network is being updated already)
+  // (the cycle-consistency word: 2 B addends, det.h; with g_det_seg its flush rides on the update launch or on the backward's segment flush)
+  if (det_on() && !g_det_seg) RUN(det_flush_range(losses, 3 * sizeof(float), sv));
+  if (optimize) RUN(adam_nets(*cfg, *b, vnets, early_v ? 1 : 2, step, sv, losses, g_det_plan.fold));  // (early: the global network is being updated already)
   else {
     hipLaunchKernelGGL(loss_total_kernel, dim3(1), dim3(1), 0, sv, losses);
     COOT_CHECK_LAUNCH("loss_total");
@@ -871,7 +976,7 @@ int coot_train_step(const coot_step_config* cfg, const coot_step_buffers* b, con
   (void)coot_net_grads_overwrite(0);
   coot_internal_set_input_stage(nullptr, nullptr, 0);
   RUN(rc_t);
-  if (optimize) RUN(adam_nets(*cfg, *b, tnets, early_t ? 1 : 2, step, st));
+  if (optimize) RUN(adam_nets(*cfg, *b, tnets, early_t ? 1 : 2, step, st, nullptr, g_det_plan.fold));
   if (repack) RUN(pack_nets(*cfg, *b, tnets, early_t ? 1 : 2, side_t));
   if (early_t) RUN(g_hops.wait(14, st));
   g_stamps.mark("text: updated", st);
@@ -970,6 +1075,8 @@ int coot_stream_destroy(coot_stream_t s) {
 }
 int coot_internal_stream_counter(int which) { return which == 0 ? g_streams.tests : (which == 1 ? g_streams.rejected : g_streams.unresolved); }
 void coot_step_grad_write(int on) { g_grad_write = on ? 1 : 0; }
+void coot_step_det_seg_flush(int on) { g_det_seg = on ? 1 : 0; }
+int coot_step_det_seg_flush_get(void) { return g_det_seg; }
 
 // text table of the last step's stamps (ms since "step starts"); synchronises the device.  Returns the number of stamps.
 int coot_debug_step_stamps(char* buf, int buf_bytes) {

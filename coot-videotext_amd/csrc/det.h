@@ -59,6 +59,28 @@ int det_set_table_pool(const DetTable& t);
 int det_set_table_rowops(const DetTable& t);
 // adds the shadow sums of the registered words inside [base, base + bytes) into them and clears the shadow (no-op while the mode is off)
 int det_flush_range(const void* base, size_t bytes, hipStream_t st);
+
+// The flush of ONE word: the fixed-point sum v joins the fp32 word in a single rounded addition (explicit: no contraction can change it).
+// det_flush_kernel and every launch that flushes words on its way (coot_train_step's update: api_step.hip) compute exactly this.
+__device__ __forceinline__ float det_fold(float w, long long v) { return __fadd_rn(w, (float)((double)v * (1.0 / kDetScale))); }
+
+// Segment flushes.  Only some words of a registered range can hold a sum — in a gradient arena whose weight matrices the backward
+// WROTE (coot_net_grads_overwrite), the biases / LayerNorm vectors between them — so a step flushes those segments, not the whole range.
+// det_locate: the shadow word of `base` when [base, base + bytes) lies inside ONE registered range (returns 1), 0 when it touches none
+// (nothing to flush), -1 when it straddles a range's end (only det_flush_range handles that)
+int det_locate(const void* base, size_t bytes, long long** shadow);
+constexpr int kDetMaxSegs = 64;
+struct DetSeg { float* p; long long* shadow; int n; int blk0; };
+struct DetSegs { int n = 0; DetSeg s[kDetMaxSegs]; };
+// adds [p, p + n) to the list (located as above; a straddling segment is flushed by det_flush_range right away on `st`)
+int det_segs_add(DetSegs& s, float* p, long n, hipStream_t st);
+// all segments of the list in ONE launch (no launch for an empty list)
+int det_flush_segs(DetSegs& s, hipStream_t st);
+// The one route that acc_add()s into a weight MATRIX in overwrite mode: launch_gemm_tn's one-pass path (fp32 atomics into C, which it
+// zero-filled first).  It notes itself here (host, this thread); the step takes the note after each backward pass and flushes that arena
+// whole.
+void det_note_matrix_atomics();
+bool det_take_matrix_atomics();
 bool det_on();
 int det_bypass_count();
 

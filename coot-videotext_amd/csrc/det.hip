@@ -12,11 +12,66 @@ __global__ __launch_bounds__(256) void det_flush_kernel(float* p, long long* sha
     const long long v = shadow[i];
     if (v != 0) {
       shadow[i] = 0;
-      p[i] += (float)((double)v * (1.0 / kDetScale));
+      p[i] = det_fold(p[i], v);
     }
   }
 }
+
+// segment s owns blocks [blk0, next blk0) of 1 024 words each
+__global__ __launch_bounds__(256) void det_flush_segs_kernel(DetSegs sg) {
+  int s = 0;
+  for (int t = 1; t < sg.n; ++t) if ((int)blockIdx.x >= sg.s[t].blk0) s = t;
+  const DetSeg& g = sg.s[s];
+  const int i0 = ((int)blockIdx.x - g.blk0) * 1024 + threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int i = i0 + k * 256;
+    if (i >= g.n) break;
+    const long long v = g.shadow[i];
+    if (v != 0) {
+      g.shadow[i] = 0;
+      g.p[i] = det_fold(g.p[i], v);
+    }
+  }
+}
+thread_local bool g_matrix_atomics = false;
 }  // namespace
+
+void det_note_matrix_atomics() { g_matrix_atomics = true; }
+bool det_take_matrix_atomics() { const bool r = g_matrix_atomics; g_matrix_atomics = false; return r; }
+
+int det_locate(const void* base, size_t bytes, long long** shadow) {
+  const char* b0 = (const char*)base;
+  *shadow = nullptr;
+  for (int i = 0; i < g_host_table.n; ++i) {
+    const DetRange& R = g_host_table.r[i];
+    if (b0 >= R.base && b0 + bytes <= R.base + R.bytes) { *shadow = R.shadow + (b0 - R.base) / 4; return 1; }
+    if (b0 < R.base + R.bytes && b0 + bytes > R.base) return -1;
+  }
+  return 0;
+}
+
+int det_segs_add(DetSegs& s, float* p, long n, hipStream_t st) {
+  if (n <= 0 || !det_on()) return 0;
+  long long* sh = nullptr;
+  const int where = det_locate(p, (size_t)n * sizeof(float), &sh);
+  if (where < 0) return det_flush_range(p, (size_t)n * sizeof(float), st);
+  if (where == 0) return 0;
+  COOT_REQUIRE(n <= (1L << 30), "det segments: %ld words", n);
+  if (s.n == kDetMaxSegs) { const int rc = det_flush_segs(s, st); if (rc) return rc; }
+  s.s[s.n++] = DetSeg{p, sh, (int)n, 0};
+  return 0;
+}
+
+int det_flush_segs(DetSegs& s, hipStream_t st) {
+  if (s.n == 0) return 0;
+  int blk = 0;
+  for (int i = 0; i < s.n; ++i) { s.s[i].blk0 = blk; blk += (s.s[i].n + 1023) / 1024; }
+  hipLaunchKernelGGL(det_flush_segs_kernel, dim3(blk), dim3(256), 0, st, s);
+  COOT_CHECK_LAUNCH("det_flush_segs");
+  s.n = 0;
+  return 0;
+}
 
 bool det_on() { return g_host_table.n > 0; }
 

@@ -1434,6 +1434,7 @@ int launch_gemm_tn(const GemmTN& g_in, hipStream_t stream) {
   // one split (global networks): the tile owner adds into C itself — no workspace, no reduce launch (needs 16-byte rows)
   const int direct = (splits == 1 && g.ldc % 4 == 0 && g.No % 4 == 0 && g.zC % 4 == 0) ? 1 : 0;
   if (direct) ws = nullptr;
+  if (!ws && !direct && det_on()) det_note_matrix_atomics();  // the one-pass path acc_add()s into C (det.h)
   void* ts = timing_begin(TIMING_TN, 2.0 * g.T * g.Mo * g.No * g.groups, 0, stream);
   if (g_tn_mode == 0)
     hipLaunchKernelGGL(gemm_tn_kernel<0>, grid, dim3(256), 0, stream, g, t_per_split, splits, ws, direct);
