@@ -92,7 +92,8 @@ class TransformerConfig:
         self.pool_dropout: float = float(pc.get("dropout", 0))
         # compute mode of the HIP network (not a reference key): "bf16" = the fast path, "f32" = the fp32 reference
         # mode (include/coot_hip.h: coot_net_config.dtype), e.g. to tell bf16 rounding from a logic error
-        # "f16": IEEE half operands = the second build of the library (COOT_OPERAND=f16 -> libcoot_hip_f16.so, forward-only); the default
+        # "f16": IEEE half operands = the second build of the library (COOT_OPERAND=f16 -> libcoot_hip_f16.so, forward-only
+        # unless the trainer runs under loss scaling: RetrievalTrainer(loss_scaler=...)); the default
         # is the format of the library the process selected, and a configuration that names the other one is refused by the library
         self.dtype: str = d.get("dtype", _lib.OPERAND_ENV)
         _require(self.dtype in ("bf16", "f16", "f32"), f"dtype {self.dtype} (bf16, f16 or f32)")

@@ -666,7 +666,7 @@ extern "C" void coot_step_det_seg_flush(int on);
 extern "C" int coot_step_det_seg_flush_get(void);
 extern "C" int coot_internal_stage_hits(void);
 extern "C" int coot_internal_stream_counter(int which);  // api_step.hip: StreamPicker
-extern "C++" { namespace coot { int det_bypass_count(); } }  // det.hip
+extern "C++" { namespace coot { int det_bypass_count(); int det_overflow_count(); int det_set_overflow_guard(int on); int det_overflow_guard(); } }  // det.hip
 int coot_get_option(const char* name, int* value) {
   if (!value) { set_error("get_option: null result"); return -1; }
   if (!strcmp(name, "tn_dma")) { *value = get_tn_dma(); return 0; }
@@ -681,7 +681,9 @@ int coot_get_option(const char* name, int* value) {
   if (!strcmp(name, "stream_unresolved")) { *value = coot_internal_stream_counter(2); return 0; }
   if (!strcmp(name, "operand_f16")) { *value = COOT_OPERAND_IS_F16; return 0; }  // which build this is (common.h)
   if (!strcmp(name, "det_seg_flush")) { *value = coot_step_det_seg_flush_get(); return 0; }
-  if (!strcmp(name, "det_bypasses")) { *value = det_bypass_count(); return 0; }  // deterministic mode: addends that took the float atomic (synchronises; -1: mode off)
+  if (!strcmp(name, "det_bypasses")) { *value = det_bypass_count(); return 0; }  // (see below)
+  if (!strcmp(name, "det_overflows")) { *value = det_overflow_count(); return 0; }  // deterministic mode: shadow adds that wrapped under the guard (synchronises; -1: mode off)
+  if (!strcmp(name, "det_overflow_check")) { *value = det_overflow_guard(); return 0; }  // deterministic mode: addends that took the float atomic (synchronises; -1: mode off)
   set_error("get_option: unknown or write-only option %s", name);
   return -2;
 }
@@ -701,7 +703,8 @@ int coot_set_option(const char* name, int value) {
   if (!strcmp(name, "tn_target_wgs")) { set_tn_target_wgs(value); return 0; }
   if (!strcmp(name, "xcd_order")) { set_xcd_order(value); return 0; }
   if (!strcmp(name, "grad_write")) { coot_step_grad_write(value); return 0; }
-  if (!strcmp(name, "det_seg_flush")) { coot_step_det_seg_flush(value); return 0; }  // 0: deterministic steps flush whole arenas in launches of their own
+  if (!strcmp(name, "det_seg_flush")) { coot_step_det_seg_flush(value); return 0; }
+  if (!strcmp(name, "det_overflow_check")) return det_set_overflow_guard(value);  // 1: wrapped fixed-point adds poison their word with NaN (det.h; synchronises)  // 0: deterministic steps flush whole arenas in launches of their own
   if (!strcmp(name, "glob_flush_aux")) { g_glob_flush_aux = value; return 0; }
   if (!strcmp(name, "pool_handover")) { g_pool_handover_on = value; return 0; }  // 0: the pack between the local and the global forward stays a launch of its own  // 0: the global network's weight-gradient launch stays on its side's stream
   if (!strcmp(name, "cl_col_split")) { set_cl_col_split(value); return 0; }
@@ -929,6 +932,9 @@ size_t coot_net_scratch_bytes(const coot_net_config* cfg, int N, int Lseq, int N
 // around its backward) makes those problems write, and coot_nets_zero_grads(..., skip_matrices = 1) zeroes only what is still
 // accumulated (biases, LayerNorm parameters: < 1 % of the arena) — one launch instead of four fills.
 static thread_local int g_grad_overwrite = 0;
+// the f16 build's backward runs only inside a loss-scaled step (api_step.hip: coot_step_set_loss_scaler); the per-op route keeps refusing
+static thread_local int g_scaled_backward = 0;
+extern "C" void coot_internal_set_scaled_backward(int on) { g_scaled_backward = on; }
 int coot_net_grads_overwrite(int on) { g_grad_overwrite = on ? 1 : 0; return 0; }
 extern "C" int coot_internal_grads_overwrite(void) { return g_grad_overwrite; }
 
@@ -1220,7 +1226,7 @@ int coot_net_bwd(const coot_net_config* cfg, const float* P, const void* wpack, 
     for (int s_ = 0; s_ < sg.n; ++s_) { rs.N[s_] = sg.N[s_]; rs.L[s_] = sg.L[s_]; rs.lens[s_] = sg.lens[s_]; }
     return ref_f32_backward(ref_desc(c, L, Ntot), P, G, feats, feats2, rs, hidden, dpooled, dhidden, dfeats, saved, saved_bytes, scratch, scratch_bytes, st);
   }
-  COOT_REQUIRE(!COOT_OPERAND_IS_F16, "net_bwd: the f16 operand build is forward-only — the reference trains its fp16 path under a GradScaler "
+  COOT_REQUIRE(!COOT_OPERAND_IS_F16 || g_scaled_backward, "net_bwd: the f16 operand build is forward-only — the reference trains its fp16 path under a GradScaler "
                "(coot/trainer_retrieval.py:277-285, nntrainer/trainer_base.py:106-109); unscaled half gradients underflow and are not offered");
   Arena AW((void*)wpack, (size_t)-1); WPack W; layout_wpack(c, AW, W);
   PerOpGuardScope perop_guard(c, W, P, wpack);

@@ -10,6 +10,7 @@
 #include "det.h"
 #include "gemm.h"
 #include "fused.h"
+#include "loss.h"
 #include "pool.h"
 #include "rowops.h"
 
@@ -555,8 +556,21 @@ struct AdamSegs {
   float* p[4]; float* g[4]; float* m[4]; float* v[4]; const float* decay[4]; const unsigned char* all1[4]; long n[4]; int blk0[5]; float* losses;
   long long* sh[4]; long long* loss_sh; int fseg0[5]; int flo[kAdamFlushSegs], fhi[kAdamFlushSegs];
 };
-__global__ __launch_bounds__(256) void adam4_kernel(AdamSegs sg, OptK k_arg, const OptK* k_dev) {
-  const OptK k = k_dev ? *k_dev : k_arg;
+// Dynamic loss scaling (coot_step_set_loss_scaler, include/coot_hip.h): the caller's device block.  scaler_check_kernel unscales the
+// gradient arenas in place and ORs inf_work; scaler_update_kernel turns that into found_inf, moves scale / growth_tracker by
+// torch.cuda.amp.GradScaler's rule (torch._amp_update_scale_) and, on a finite optimizer step, advances the step count and the
+// optimizer scalars the update launches read.  A step with found_inf set leaves every parameter and moment word alone.
+struct ScalerBlock {
+  float scale; int growth_tracker; int found_inf; int skipped;
+  float growth_factor, backoff_factor; int growth_interval; int inf_work;
+  long long step; int pad[2];
+  OptK k;
+};
+static_assert(sizeof(ScalerBlock) == 80, "coot_step_loss_scaler_bytes: layout documented in include/coot_hip.h");
+thread_local ScalerBlock* g_scaler = nullptr;
+
+__global__ __launch_bounds__(256) void adam4_kernel(AdamSegs sg, OptK k_arg, const OptK* k_dev, const ScalerBlock* sc) {
+  const OptK k = sc ? sc->k : (k_dev ? *k_dev : k_arg);
   int s = 0;
 #pragma unroll
   for (int t = 1; t < 4; ++t) if ((int)blockIdx.x >= sg.blk0[t]) s = t;
@@ -569,6 +583,7 @@ __global__ __launch_bounds__(256) void adam4_kernel(AdamSegs sg, OptK k_arg, con
       }
     sg.losses[0] = sg.losses[1] + sg.losses[2];
   }
+  if (sc && sc->found_inf) return;  // loss scaling: a non-finite gradient skips the whole step (the arenas were flushed by the check)
   const long n = sg.n[s];
   const int blk = (int)blockIdx.x - sg.blk0[s];
   const long i = ((long)blk * 256 + threadIdx.x) * 4;
@@ -629,12 +644,99 @@ __global__ void step_state_kernel(StepState* s, int optimizer, int degen, float 
   s->k = opt_scalars(optimizer, degen, s->lr, b1, b2, eps, wd, (int64_t)s->step);
 }
 
+// Loss scaling, part 1: GradScaler.unscale_ of the arenas in place + the non-finite check, in adam4_kernel's geometry (a fixed grid:
+// one workgroup per 1 024 words).  Deterministic mode: the fixed-point sums of the words first (the same fold as adam4_kernel's), so the
+// update launch behind it finds nothing to flush.  found: an integer OR (no float atomics; the result does not depend on the order).
+__global__ __launch_bounds__(256) void scaler_check_kernel(AdamSegs sg, ScalerBlock* sc) {
+  int s = 0;
+#pragma unroll
+  for (int t = 1; t < 4; ++t) if ((int)blockIdx.x >= sg.blk0[t]) s = t;
+  const long n = sg.n[s];
+  const int blk = (int)blockIdx.x - sg.blk0[s];
+  const long i = ((long)blk * 256 + threadIdx.x) * 4;
+  if (i >= n) return;
+  float* g = sg.g[s];
+  if (long long* sh = sg.sh[s]) {
+    const long b0 = (long)blk * 1024, b1 = b0 + 1024;
+    for (int q = sg.fseg0[s]; q < sg.fseg0[s + 1]; ++q) {
+      const long lo = sg.flo[q], hi = sg.fhi[q];
+      if (lo >= b1 || hi <= b0) continue;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const long e = i + j;
+        if (e < lo || e >= hi || e >= n) continue;
+        const long long v = sh[e];
+        if (v != 0) { sh[e] = 0; g[e] = det_fold(g[e], v); }
+      }
+    }
+  }
+  const float inv = 1.f / sc->scale;  // (GradScaler: scale.double().reciprocal().float(); the scale is a power of two in practice)
+  bool bad = false;
+  if (i + 3 < n) {
+    f32x4_t v = *reinterpret_cast<f32x4_t*>(g + i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { v[j] *= inv; bad |= !isfinite(v[j]); }
+    *reinterpret_cast<f32x4_t*>(g + i) = v;
+  } else {
+    for (long e = i; e < n; ++e) { const float v = g[e] * inv; g[e] = v; bad |= !isfinite(v); }
+  }
+  if (bad) atomicOr(&sc->inf_work, 1);
+}
+
+// Loss scaling, part 2 (one thread, behind the check): found_inf for the step; on an optimizer step the scale schedule of
+// torch._amp_update_scale_ (what GradScaler.update calls) and, if the step is finite, step += 1 with the optimizer scalars of it.
+// lr_dev: the device state block's learning rate in a replayable step, else null (lr).
+__global__ void scaler_update_kernel(ScalerBlock* sc, int optimize, int optimizer, int degen, float lr, const float* lr_dev, float b1, float b2,
+                                     float eps, float wd) {
+  const int found = sc->inf_work != 0;
+  sc->inf_work = 0;
+  sc->found_inf = found;
+  if (!optimize) return;
+  if (found) {
+    sc->scale = sc->scale * sc->backoff_factor;
+    sc->growth_tracker = 0;
+    sc->skipped += 1;
+    return;
+  }
+  const int successful = sc->growth_tracker + 1;
+  if (successful == sc->growth_interval) {
+    const float grown = sc->scale * sc->growth_factor;
+    if (isfinite(grown)) sc->scale = grown;
+    sc->growth_tracker = 0;
+  } else {
+    sc->growth_tracker = successful;
+  }
+  sc->step += 1;
+  sc->k = opt_scalars(optimizer, degen, lr_dev ? *lr_dev : lr, b1, b2, eps, wd, (int64_t)sc->step);
+}
+
+int build_segs(const coot_step_config& cfg, const coot_step_buffers& b, const int* nets, int count, hipStream_t st, float* losses, bool flush,
+               AdamSegs& sg, int& grid);  // below
+// the check over the four gradient arenas, on `st` behind everything that wrote them
+int scaler_check(const coot_step_config& cfg, const coot_step_buffers& b, bool optimize, hipStream_t st) {
+  const int nets[4] = {0, 1, 2, 3};
+  AdamSegs sg; int blk = 0;
+  RUN(build_segs(cfg, b, nets, 4, st, nullptr, true, sg, blk));
+  hipLaunchKernelGGL(scaler_check_kernel, dim3(blk), dim3(256), 0, st, sg, g_scaler);
+  COOT_CHECK_LAUNCH("scaler_check");
+  hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(1), 0, st, g_scaler, optimize ? 1 : 0, cfg.optimizer, cfg.radam_degentosgd, cfg.lr,
+                     g_state_dev ? (const float*)&g_state_dev->lr : (const float*)nullptr, cfg.beta1, cfg.beta2, cfg.eps, cfg.weight_decay);
+  COOT_CHECK_LAUNCH("scaler_update");
+  return 0;
+}
+// the f16 build's backward runs inside a scaled step only (api.hip: net_bwd); cleared on every exit path
+extern "C" void coot_internal_set_scaled_backward(int on);  // api.hip
+struct ScaledBwdScope {
+  explicit ScaledBwdScope(bool on) { coot_internal_set_scaled_backward(on ? 1 : 0); }
+  ~ScaledBwdScope() { coot_internal_set_scaled_backward(0); }
+};
+
 // Adam update of `count` parameter arenas in ONE launch (four dependent 13 us launches used to end the step)
 // flush: deterministic mode with g_det_seg — the launch first flushes the fixed-point sums of the arenas it reads (g_det_plan) and of
 // the loss words (a segment list that does not fit, or an arena that straddles a registered range: a flush launch of its own in front)
-int adam_nets(const coot_step_config& cfg, const coot_step_buffers& b, const int* nets, int count, int64_t step, hipStream_t st,
-              float* losses = nullptr, bool flush = false) {
-  AdamSegs sg;
+// the launch geometry of adam4_kernel / scaler_check_kernel over `count` arenas (one workgroup per 1 024 words); returns the grid size
+int build_segs(const coot_step_config& cfg, const coot_step_buffers& b, const int* nets, int count, hipStream_t st, float* losses, bool flush,
+               AdamSegs& sg, int& grid) {
   sg.losses = losses;
   sg.loss_sh = nullptr;
   flush = flush && det_on();
@@ -669,8 +771,16 @@ int adam_nets(const coot_step_config& cfg, const coot_step_buffers& b, const int
   }
   sg.blk0[4] = blk; sg.fseg0[4] = nseg;
   RUN(det_flush_segs(spill, st));
+  grid = blk;
+  return 0;
+}
+int adam_nets(const coot_step_config& cfg, const coot_step_buffers& b, const int* nets, int count, int64_t step, hipStream_t st,
+              float* losses = nullptr, bool flush = false) {
+  AdamSegs sg; int blk = 0;
+  RUN(build_segs(cfg, b, nets, count, st, losses, flush, sg, blk));
   const OptK k = opt_scalars(cfg.optimizer, cfg.radam_degentosgd, cfg.lr, cfg.beta1, cfg.beta2, cfg.eps, cfg.weight_decay, step);
-  hipLaunchKernelGGL(adam4_kernel, dim3(blk), dim3(256), 0, st, sg, k, g_state_dev ? (const OptK*)&g_state_dev->k : (const OptK*)nullptr);
+  hipLaunchKernelGGL(adam4_kernel, dim3(blk), dim3(256), 0, st, sg, k, g_state_dev ? (const OptK*)&g_state_dev->k : (const OptK*)nullptr,
+                     (const ScalerBlock*)g_scaler);
   COOT_CHECK_LAUNCH("adam4");
   return 0;
 }
@@ -768,7 +878,9 @@ int coot_step_backward(const coot_step_config* cfg, const coot_step_buffers* b, 
                        void* workspace, size_t workspace_bytes, int train, uint64_t seed, coot_stream_t main_s, coot_stream_t side_v,
                        coot_stream_t side_t) {
   RUN(check_cfg(*cfg));
-  COOT_REQUIRE(!COOT_OPERAND_IS_F16, "coot_step_backward: the f16 operand build is forward-only (no GradScaler: coot/trainer_retrieval.py:277-285); coot_step_forward runs");
+  COOT_REQUIRE(!COOT_OPERAND_IS_F16 || g_scaler, "coot_step_backward: the f16 operand build is forward-only without a loss scaler (GradScaler: "
+               "coot/trainer_retrieval.py:277-285; coot_step_set_loss_scaler); coot_step_forward runs");
+  ScaledBwdScope scaled_bwd(g_scaler != nullptr);
   Bump A(workspace, workspace_bytes); StepWs W; layout_step(*cfg, *d, A, W);
   const SidePacked pk = side_packed(*x, *d);
   COOT_REQUIRE(!A.overflow, "step: workspace too small");
@@ -801,6 +913,12 @@ int coot_step_update(const coot_step_config* cfg, const coot_step_buffers* b, in
                "step_update: unknown bits in repack (%d): a bit mask since ABI 5", repack);
   hipStream_t sm = (hipStream_t)main_s, sv = (hipStream_t)side_v, st = (hipStream_t)side_t;
   const bool do_pack = (repack & COOT_UPDATE_REPACK) != 0;
+  if (g_scaler) {
+    // loss scaling: the update is all or nothing, decided over the four arenas in front of it (main_s is ordered behind all of them)
+    COOT_REQUIRE((repack & (COOT_UPDATE_GLOBAL_ONLY | COOT_UPDATE_SKIP_GLOBAL)) == 0, "step_update: with a loss scaler the four networks are updated "
+                 "together behind the non-finite check — no early update of the global networks (COOT_UPDATE_GLOBAL_ONLY / SKIP_GLOBAL)");
+    RUN(scaler_check(*cfg, *b, true, sm));
+  }
   if (repack & COOT_UPDATE_GLOBAL_ONLY) {
     // the two GLOBAL networks only, on main_s alone: their gradients are final (and, data parallel, reduced) a whole local backward
     // before the step's end — the caller runs this on its communication stream behind their bucket (as coot_train_step's early update)
@@ -839,7 +957,9 @@ int coot_train_step(const coot_step_config* cfg, const coot_step_buffers* b, con
                     float* losses, void* workspace, size_t workspace_bytes, int train, uint64_t seed, int64_t step, int do_optimizer,
                     coot_stream_t main_s, coot_stream_t side_v, coot_stream_t side_t) {
   RUN(check_cfg(*cfg));
-  COOT_REQUIRE(!COOT_OPERAND_IS_F16, "coot_train_step: the f16 operand build is forward-only (no GradScaler: coot/trainer_retrieval.py:277-285); coot_step_forward runs");
+  COOT_REQUIRE(!COOT_OPERAND_IS_F16 || g_scaler, "coot_train_step: the f16 operand build is forward-only without a loss scaler (GradScaler: "
+               "coot/trainer_retrieval.py:277-285; coot_step_set_loss_scaler); coot_step_forward runs");
+  ScaledBwdScope scaled_bwd(g_scaler != nullptr);
   COOT_REQUIRE(losses, "train_step: losses pointer");
   COOT_REQUIRE((do_optimizer & ~(COOT_STEP_OPTIMIZER | COOT_STEP_REPACK | COOT_STEP_PACKS_FRESH | COOT_STEP_DEFER_TEXT_JOIN | COOT_STEP_INPUT_STAGES |
                                  COOT_STEP_STAGE_ANNOUNCED)) == 0, "train_step: unknown bits in do_optimizer (%d)", do_optimizer);
@@ -943,7 +1063,8 @@ int coot_train_step(const coot_step_config* cfg, const coot_step_buffers* b, con
   // captured step)
   struct DetScope { ~DetScope() { g_det_plan = DetPlan{}; } } det_scope;
   g_det_plan.fold = optimize && g_det_seg; g_det_plan.losses = losses;
-  const bool early = optimize && (!det_on() || g_det_seg) && !g_state_dev;
+  // (loss scaling: no early update — the step is all or nothing, decided behind BOTH sides' backward)
+  const bool early = optimize && (!det_on() || g_det_seg) && !g_state_dev && !g_scaler;
   const bool early_v = early && (long)d->B * d->Lv + (long)d->Nc * d->Lc >= kEarlyMinTokens;
   const bool early_t = early && (long)d->B * d->Lp + (long)d->Nc * d->Ls >= kEarlyMinTokens;
   struct EarlyScope { ~EarlyScope() { g_early = EarlyUpdate{}; } } early_scope;
@@ -961,12 +1082,14 @@ int coot_train_step(const coot_step_config* cfg, const coot_step_buffers* b, con
   // side only — all three loss words are readable there on return (on the text side's launch, losses[0] raced with a deferred join)
   // (the cycle-consistency word: 2 B addends, det.h; with g_det_seg its flush rides on the update launch or on the backward's segment flush)
   if (det_on() && !g_det_seg) RUN(det_flush_range(losses, 3 * sizeof(float), sv));
-  if (optimize) RUN(adam_nets(*cfg, *b, vnets, early_v ? 1 : 2, step, sv, losses, g_det_plan.fold));  // (early: the global network is being updated already)
+  if (g_scaler) {
+    // loss scaling: nothing is updated before the text side's gradients are checked too (below)
+  } else if (optimize) RUN(adam_nets(*cfg, *b, vnets, early_v ? 1 : 2, step, sv, losses, g_det_plan.fold));  // (early: the global network is being updated already)
   else {
     hipLaunchKernelGGL(loss_total_kernel, dim3(1), dim3(1), 0, sv, losses);
     COOT_CHECK_LAUNCH("loss_total");
   }
-  if (repack) RUN(pack_nets(*cfg, *b, vnets, early_v ? 1 : 2, side_v));
+  if (repack && !g_scaler) RUN(pack_nets(*cfg, *b, vnets, early_v ? 1 : 2, side_v));
   if (early_v) RUN(g_hops.wait(13, sv));
   g_stamps.mark("video: updated", sv);
   if (piped) coot_internal_set_input_stage(SL.xt, SL.pt, 0);
@@ -976,8 +1099,23 @@ int coot_train_step(const coot_step_config* cfg, const coot_step_buffers* b, con
   (void)coot_net_grads_overwrite(0);
   coot_internal_set_input_stage(nullptr, nullptr, 0);
   RUN(rc_t);
-  if (optimize) RUN(adam_nets(*cfg, *b, tnets, early_t ? 1 : 2, step, st, nullptr, g_det_plan.fold));
-  if (repack) RUN(pack_nets(*cfg, *b, tnets, early_t ? 1 : 2, side_t));
+  if (g_scaler) {
+    // loss scaling: both sides' gradients -> unscale + non-finite check -> the four networks' update (or none), on the video stream;
+    // the text stream is ordered behind it (a deferred join then still orders everything of the step)
+    RUN(g_hops.hop(8, st, sv));
+    RUN(scaler_check(*cfg, *b, optimize, sv));
+    const int all4[4] = {0, 1, 2, 3};
+    if (optimize) RUN(adam_nets(*cfg, *b, all4, 4, step, sv, losses, g_det_plan.fold));
+    else {
+      hipLaunchKernelGGL(loss_total_kernel, dim3(1), dim3(1), 0, sv, losses);
+      COOT_CHECK_LAUNCH("loss_total");
+    }
+    if (repack) RUN(pack_nets(*cfg, *b, all4, 4, side_v));
+    g_stamps.mark("video: updated", sv);
+    RUN(g_hops.hop(15, sv, st));
+  }
+  if (optimize && !g_scaler) RUN(adam_nets(*cfg, *b, tnets, early_t ? 1 : 2, step, st, nullptr, g_det_plan.fold));
+  if (repack && !g_scaler) RUN(pack_nets(*cfg, *b, tnets, early_t ? 1 : 2, side_t));
   if (early_t) RUN(g_hops.wait(14, st));
   g_stamps.mark("text: updated", st);
   RUN(g_hops.hop(4, sv, sm));
@@ -995,6 +1133,17 @@ int coot_step_set_device_state(void* state) {
   return 0;
 }
 int coot_step_set_cycle_indices(const int64_t* idx) { g_cc_idx_inject = idx; return 0; }
+size_t coot_step_loss_scaler_bytes(void) { return sizeof(ScalerBlock); }
+int coot_step_set_loss_scaler(void* block) {
+  g_scaler = (ScalerBlock*)block;
+  set_loss_grad_scale(block ? &g_scaler->scale : nullptr);
+  return 0;
+}
+int coot_step_unscale_grads(const coot_step_config* cfg, const coot_step_buffers* b, coot_stream_t stream) {
+  RUN(check_cfg(*cfg));
+  COOT_REQUIRE(g_scaler, "step_unscale_grads: no loss scaler set (coot_step_set_loss_scaler)");
+  return scaler_check(*cfg, *b, false, (hipStream_t)stream);
+}
 size_t coot_step_input_stage_bytes(const coot_step_config* cfg, const coot_step_dims* dims) {
   if (!cfg || !dims) return 0;
   return stage_layout(*cfg, *dims, nullptr).bytes;

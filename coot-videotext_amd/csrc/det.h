@@ -14,19 +14,29 @@
 // up as NaN / Inf in the gradients and the loss exactly as without the mode (the run is no longer bit-reproducible then — it is lost anyway).
 // Every such addend is COUNTED (a word in the shadow's padding; coot_get_option("det_bypasses") reads it, synchronising): a caller
 // that relies on bit-reproducibility checks that the count stayed 0 (RetrievalTrainer.det_bypass_count).
+// The 64-bit word itself wraps past +-2^23 (in value units).  With the overflow guard on (coot_set_option("det_overflow_check", 1):
+// what a loss-scaled deterministic run turns on, where a scaled word can get there) every shadow add reads the old word back, and an
+// add whose sum wraps sets the fp32 word to NaN (and is counted: coot_get_option("det_overflows")) — the wrapped, finite garbage the
+// flush would otherwise fold in becomes a non-finite gradient that the loss scaler's check sees and skips.  Off, the add returns nothing
+// (the unscaled path: no word reaches 2^23 there) and costs what it always did.
 #pragma once
 #include "common.h"
 
 namespace coot {
 
 struct DetRange { const char* base; size_t bytes; long long* shadow; };
-struct DetTable { int n; DetRange r[8]; unsigned* bypass; };  // bypass: counts the addends that left the fixed-point path (below), in the shadow's padding
+struct DetTable {
+  int n; DetRange r[8];
+  unsigned* bypass;    // counts the addends that left the fixed-point path (below), in the shadow's padding
+  int guard;           // overflow guard on (above)
+  unsigned* overflow;  // counts the wrapped adds (next to bypass)
+};
 constexpr double kDetScale = 1099511627776.0;  // 2^40
 constexpr float kDetMaxAddend = 4194304.0f;    // 2^22: one addend; the 64-bit word itself holds sums up to +-8.4e6
 
 // one table per translation unit (the library is built without relocatable device code): COOT_DET_DEFINE_SETTER(name) defines
 // det_set_table_<name>(), det.hip installs the same table in all of them
-static __device__ DetTable g_det_dev = {0, {}, nullptr};
+static __device__ DetTable g_det_dev = {0, {}, nullptr, 0, nullptr};
 
 __device__ __forceinline__ void acc_add(float* p, float v) {
   const int n = g_det_dev.n;
@@ -40,7 +50,17 @@ __device__ __forceinline__ void acc_add(float* p, float v) {
         atomicAdd(g_det_dev.bypass, 1u);
         break;
       }
-      atomicAdd(reinterpret_cast<unsigned long long*>(g_det_dev.r[i].shadow + (off >> 2)), (unsigned long long)llrint((double)v * kDetScale));
+      unsigned long long* w = reinterpret_cast<unsigned long long*>(g_det_dev.r[i].shadow + (off >> 2));
+      const unsigned long long a = (unsigned long long)llrint((double)v * kDetScale);
+      if (g_det_dev.guard) {
+        const unsigned long long old = atomicAdd(w, a), sum = old + a;
+        if ((long long)((old ^ sum) & (a ^ sum)) < 0) {  // signed overflow of old + a: the word no longer holds the sum
+          atomicAdd(g_det_dev.overflow, 1u);
+          atomicAdd(p, __builtin_nanf(""));
+        }
+      } else {
+        atomicAdd(w, a);
+      }
       return;
     }
   }
@@ -83,5 +103,8 @@ void det_note_matrix_atomics();
 bool det_take_matrix_atomics();
 bool det_on();
 int det_bypass_count();
+int det_overflow_count();                    // wrapped adds since coot_det_configure (synchronises; -1: mode off)
+int det_set_overflow_guard(int on);          // uploads the table (synchronises the device): a setup call
+int det_overflow_guard();
 
 }  // namespace coot

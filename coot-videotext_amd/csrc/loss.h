@@ -20,8 +20,14 @@ struct CycleArgs {
   float* rows_sent = nullptr;  // optional [B, Cs]
   float* dclip = nullptr;   // [B, Cc, D] += grad (may be null: forward only)
   float* dsent = nullptr;   // [B, Cs, D]
+  const float* grad_scale = nullptr;  // device word the gradient seed is multiplied by (loss scaling), or null: unscaled
 };
 int launch_cyclecons(const CycleArgs& a, hipStream_t st);
+
+// Loss scaling (coot_step_set_loss_scaler): while a device scale word is set (thread-local), the backward launches of both losses
+// multiply the gradient they seed by it — the loss words themselves stay unscaled.  Null: the kernels compute what they always did.
+void set_loss_grad_scale(const float* scale_dev);
+const float* loss_grad_scale();
 
 // compute_total_constrastive_loss in three launches (loss_fused.hip).  v / dv: the six sets in the order vid_emb, par_emb,
 // clip_emb, sent_emb, vid_ctx, par_ctx (dv all null = forward only; gradients are ACCUMULATED).  w_pair[p] / w_self[p]:

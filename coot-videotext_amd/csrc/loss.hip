@@ -97,7 +97,8 @@ __global__ __launch_bounds__(256) void cyclecons_kernel(CycleArgs a) {
   __syncthreads();
   float* dsrc = dir == 0 ? a.dclip + (long)b * a.Cc * D : a.dsent + (long)b * a.Cs * D;
   float* dtgt = dir == 0 ? a.dsent + (long)b * a.Cs * D : a.dclip + (long)b * a.Cc * D;
-  const float dmu = wred[0][0];
+  float dmu = wred[0][0];
+  if (a.grad_scale) dmu *= *a.grad_scale;  // loss scaling: every gradient below is linear in d loss / d mu
   __syncthreads();
   // ddist2_k = beta_k (dbeta_k - sum beta dbeta), dbeta_k = dmu * k ; zero for masked k
   if (threadIdx.x == 0) {
@@ -161,12 +162,20 @@ __global__ __launch_bounds__(256) void cyclecons_kernel(CycleArgs a) {
   }
 }
 
+namespace {
+thread_local const float* g_loss_grad_scale = nullptr;
+}  // namespace
+void set_loss_grad_scale(const float* scale_dev) { g_loss_grad_scale = scale_dev; }
+const float* loss_grad_scale() { return g_loss_grad_scale; }
+
 int launch_cyclecons(const CycleArgs& a, hipStream_t st) {
   COOT_REQUIRE(a.clip && a.sent && a.clip_lens && a.sent_lens && a.idx_clip && a.idx_sent && a.loss, "cyclecons: null pointer");
   COOT_REQUIRE(a.Cc <= CC_MAXC && a.Cs <= CC_MAXC && a.D <= 1024, "cyclecons: at most %d clips/sentences per video and D<=1024 (Cc=%d Cs=%d D=%d)", CC_MAXC, a.Cc, a.Cs, a.D);
   COOT_REQUIRE((a.dclip == nullptr) == (a.dsent == nullptr), "cyclecons: dclip/dsent must both be set or both null");
   if (a.B <= 0) return 0;
-  hipLaunchKernelGGL(cyclecons_kernel, dim3(a.B, 2), dim3(256), 0, st, a);
+  CycleArgs la = a;
+  if (la.dclip && !la.grad_scale) la.grad_scale = loss_grad_scale();
+  hipLaunchKernelGGL(cyclecons_kernel, dim3(la.B, 2), dim3(256), 0, st, la);
   COOT_CHECK_LAUNCH("cyclecons");
   return 0;
 }

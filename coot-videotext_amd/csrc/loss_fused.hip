@@ -534,7 +534,8 @@ __global__ __launch_bounds__(64 * CLS_NW) void cl_small_kernel(ClSmallArgs A) {
 // per set: up to 3 contributions  coef * dX_h[i] + dcoef * (c1_p[i] + c1_q[i]) * other[i]   (other = bf16 normalised rows)
 struct ClContrib { const float* dX; float coef; const float* c1p; const float* c1q; float dcoef; const bf16_t* other; int cs; long dxs, c1s; };  // cs partials, strides dxs / c1s
 struct ClSet { const float* v; long ldv; const float* inv; float* dv; int N, d, nc, row0, w0, wn; ClContrib c[3]; };  // dv: rows [w0, w0 + wn) only, compact
-struct ClFinishArgs { ClSet s[6]; int rows; const float* loss_part[CL_MAX_HALF]; int loss_n[CL_MAX_HALF]; float loss_coef[CL_MAX_HALF]; int nl; float* loss; };
+struct ClFinishArgs { ClSet s[6]; int rows; const float* loss_part[CL_MAX_HALF]; int loss_n[CL_MAX_HALF]; float loss_coef[CL_MAX_HALF]; int nl; float* loss;
+                     const float* grad_scale; /* loss scaling: the rows' gradients are multiplied by this device word (null: not) */ };
 
 __global__ __launch_bounds__(256) void cl_finish_kernel(ClFinishArgs A) {
   const int lane = threadIdx.x & 63;
@@ -612,10 +613,11 @@ __global__ __launch_bounds__(256) void cl_finish_kernel(ClFinishArgs A) {
     }
   }
   dot = wave_sum(dot);
+  const float ginv = A.grad_scale ? inv * *A.grad_scale : inv;
 #pragma unroll
   for (int q = 0; q < MAXC; ++q) {
     const int ch = lane + 64 * q;
-    if (ch < nch) *reinterpret_cast<f32x4_t*>(S.dv + (long)(row - S.w0) * d + ch * 4) = old[q] + (g[q] - a[q] * dot) * inv;
+    if (ch < nch) *reinterpret_cast<f32x4_t*>(S.dv + (long)(row - S.w0) * d + ch * 4) = old[q] + (g[q] - a[q] * dot) * ginv;
   }
 }
 
@@ -807,6 +809,7 @@ int launch_contrastive_fused(const float* const v[6], float* const dv[6], int n_
     }
   }
   fa.rows = frows;
+  fa.grad_scale = bwd ? loss_grad_scale() : nullptr;
   hipLaunchKernelGGL(cl_finish_kernel, dim3((frows + 3) / 4 + 1), dim3(256), 0, st, fa);  // + the loss workgroup
   COOT_CHECK_LAUNCH("cl_finish");
   return 0;

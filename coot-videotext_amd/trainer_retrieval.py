@@ -118,6 +118,88 @@ def _with_next(iterable):
     yield cur, None
 
 
+class LossScaler:
+    """Dynamic loss scaling of the native step, with torch.cuda.amp.GradScaler's rules and constructor arguments (the reference
+    trains its fp16 path under one: coot/trainer_retrieval.py:264,277-285).  Everything is decided on the device, in a block the
+    library reads and writes (include/coot_hip.h: coot_step_set_loss_scaler): the loss gradients are seeded times ``scale``, the
+    gradient arenas are unscaled in place behind the backward, a step with a NaN / Inf gradient is skipped (no parameter or moment
+    word moves, the optimizer step count stays) and backs the scale off, ``growth_interval`` finite steps in a row grow it.
+    ``growth_factor = backoff_factor = 1`` holds a fixed scale.  Opt-in: RetrievalTrainer(cfg, mgr, loss_scaler=LossScaler()) or
+    trainer.enable_loss_scaling()."""
+
+    _FMT = "<fiiiffiiqii"  # scale, growth_tracker, found_inf, skipped, growth_factor, backoff_factor, growth_interval, work, step, pad[2]
+
+    def __init__(self, init_scale: float = 2.0 ** 16, growth_factor: float = 2.0, backoff_factor: float = 0.5, growth_interval: int = 2000):
+        if not init_scale > 0 or not growth_factor >= 1.0 or not 0.0 < backoff_factor <= 1.0 or int(growth_interval) < 1:
+            raise ValueError(f"LossScaler: init_scale > 0, growth_factor >= 1, 0 < backoff_factor <= 1, growth_interval >= 1 "
+                             f"({init_scale}, {growth_factor}, {backoff_factor}, {growth_interval})")
+        self._host = {"scale": float(init_scale), "growth_factor": float(growth_factor), "backoff_factor": float(backoff_factor),
+                      "growth_interval": int(growth_interval), "_growth_tracker": 0, "skipped_steps": 0, "step": None}
+        self.block: Optional[torch.Tensor] = None  # device block (created by the first native step)
+
+    def _ensure(self, device, step: int) -> torch.Tensor:
+        """The device block, created from the host state; `step` = optimizer steps the trainer has taken (used unless the state
+        that was loaded carries its own)."""
+        if self.block is None or self.block.device != torch.device(device):
+            import struct
+            lib = _lib.load()
+            n = int(lib.coot_step_loss_scaler_bytes())
+            h = self._host if self.block is None else self._read()
+            st = h["step"] if h["step"] is not None else step
+            hdr = struct.pack(self._FMT, h["scale"], h["_growth_tracker"], 0, h["skipped_steps"], h["growth_factor"], h["backoff_factor"],
+                              h["growth_interval"], 0, int(st), 0, 0)
+            blk = torch.zeros(n, dtype=torch.uint8)
+            blk[:len(hdr)] = torch.frombuffer(bytearray(hdr), dtype=torch.uint8)
+            self.block = blk.to(device)
+        return self.block
+
+    def _read(self) -> Dict[str, Any]:
+        """The block's words (synchronises the device); the host state while no block exists."""
+        if self.block is None:
+            return dict(self._host)
+        import struct
+        vals = struct.unpack(self._FMT, bytes(self.block[:struct.calcsize(self._FMT)].cpu().numpy().tobytes()))
+        return {"scale": vals[0], "_growth_tracker": vals[1], "found_inf": vals[2], "skipped_steps": vals[3], "growth_factor": vals[4],
+                "backoff_factor": vals[5], "growth_interval": vals[6], "step": vals[8]}
+
+    def get_scale(self) -> float:
+        return float(self._read()["scale"])
+
+    def skipped_steps(self) -> int:
+        return int(self._read()["skipped_steps"])
+
+    def found_inf(self) -> bool:
+        """Whether the last native step saw a non-finite gradient (synchronises)."""
+        return bool(self._read().get("found_inf", 0))
+
+    def state_dict(self) -> Dict[str, Any]:
+        """GradScaler.state_dict()'s keys (scale, growth_factor, backoff_factor, growth_interval, _growth_tracker) plus the
+        skipped-step count and the device-side optimizer step count (None before the first native step)."""
+        h = self._read()
+        return {k: h[k] for k in ("scale", "growth_factor", "backoff_factor", "growth_interval", "_growth_tracker", "skipped_steps", "step")}
+
+    def load_state_dict(self, state: Dict[str, Any]) -> None:
+        h = dict(self._host)
+        for k in ("scale", "growth_factor", "backoff_factor"):
+            h[k] = float(state[k])
+        h["growth_interval"] = int(state["growth_interval"])
+        h["_growth_tracker"] = int(state.get("_growth_tracker", 0))
+        h["skipped_steps"] = int(state.get("skipped_steps", 0))
+        # a GradScaler state carries no step count: the optimizer steps already taken stay what they are
+        h["step"] = int(state["step"]) if state.get("step") is not None else self._read()["step"]
+        self._host = h
+        if self.block is not None:  # rewritten from the host state, on the same device
+            dev, self.block = self.block.device, None
+            self._ensure(dev, 0)
+
+    def _set_step(self, step: int) -> None:
+        """The optimizer steps already taken (the trainer's count, when it hands the scaler its steps)."""
+        if self.block is None:
+            self._host["step"] = int(step)
+        else:
+            self.load_state_dict(dict(self._read(), step=int(step)))
+
+
 class RetrievalTrainer:
     # data-parallel native step: Adam + weight pack of the global networks on the communication stream behind their gradient bucket
     # (COOT_UPDATE_GLOBAL_ONLY), as coot_train_step does on one GPU.  Built and parity-tested in round 5; with ONE rank it measured 0.5 %
@@ -129,8 +211,9 @@ class RetrievalTrainer:
     _stage_owner = None  # id() of the trainer whose input stages the library currently holds (thread-local there; one training thread here)
 
     def __init__(self, cfg: RetrievalConfig, model_mgr: RetrievalModelManager, is_test: bool = False,
-                 world_size: int = 1):
+                 world_size: int = 1, loss_scaler: Optional[LossScaler] = None):
         self.cfg = cfg
+        self.loss_scaler: Optional[LossScaler] = loss_scaler  # dynamic loss scaling of the native step (None: off)
         self.model_mgr = model_mgr
         self.loss_cfg = loss_fn.ContrastiveLossConfig.from_section(cfg.train.contrastive_loss_config)
         self.loss_contr = loss_fn.ContrastiveLoss(self.loss_cfg.margin)
@@ -261,7 +344,9 @@ class RetrievalTrainer:
         This is the AUTOGRAD route (torch autograd + torch.optim around the library's per-network calls): always eager.  A captured
         (hipGraph) step exists on the native route only — train_step_native(use_graph=True), one C call inside the capture; the
         autograd route's whole-step capture (rounds 1-5) was removed in round 6: its replay crashed inside hipGraphLaunch under one
-        test ordering and was never root-caused (docs/NOTEBOOK_r1-r5.md 12), and nothing defaulted to it."""
+        test ordering and was never root-caused (docs/NOTEBOOK_r1-r5.md 12), and nothing defaulted to it.
+        Loss scaling (self.loss_scaler) is a feature of the native routes only: this route ignores it, and in the IEEE-half build
+        (COOT_OPERAND=f16) its backward keeps refusing ("forward-only")."""
         return self._step_impl(batch, vid_counts, clip_counts)
 
     def _step_prepare_seed(self, batch, nets) -> None:
@@ -522,6 +607,67 @@ class RetrievalTrainer:
             _lib.check(lib.coot_step_set_next_batch(None, None), "coot_step_set_next_batch")
         return True
 
+    # ---- dynamic loss scaling of the native step (LossScaler; include/coot_hip.h: coot_step_set_loss_scaler) ----------------------
+    def enable_loss_scaling(self, scaler: Optional[LossScaler] = None, **kwargs) -> LossScaler:
+        """Turns loss scaling on for the native routes (train_step_native, its graph replay and the data-parallel phases; also what
+        train_model runs): ``scaler`` or LossScaler(**kwargs).  The IEEE-half build (COOT_OPERAND=f16) trains only this way.  The
+        per-op autograd route (train_step) is not scaled: in the f16 build its backward keeps refusing."""
+        if scaler is None:
+            scaler = LossScaler(**kwargs)
+        elif kwargs:
+            raise ValueError("enable_loss_scaling: a scaler or its constructor arguments, not both")
+        self.disable_loss_scaling()  # (the trainer's step count first catches up with a scaler that was active until now)
+        self._drop_graphs()  # (a captured step carries the scaler it was captured with)
+        st = getattr(self, "_native", None)
+        if st is not None:  # the optimizer steps this trainer has taken — also when the scaler ran elsewhere before (Adam's bias correction)
+            scaler._set_step(int(st.step))
+        self.loss_scaler = scaler
+        return scaler
+
+    def disable_loss_scaling(self) -> None:
+        """Back to unscaled native steps; the optimizer step count continues from the device's."""
+        sc = self.loss_scaler
+        if sc is None:
+            return
+        self._drop_graphs()
+        st = getattr(self, "_native", None)
+        if st is not None and sc.block is not None:
+            st.step = int(sc.state_dict()["step"])
+        self.loss_scaler = None
+        self._det_overflow_guard(False)
+
+    def loss_scale(self) -> float:
+        """The current loss scale (device word: synchronises — for logging and tests, not for the step)."""
+        assert self.loss_scaler is not None, "loss scaling is off"
+        return self.loss_scaler.get_scale()
+
+    def skipped_steps(self) -> int:
+        """Optimizer steps skipped for a non-finite gradient since the scaler was created (device word: synchronises)."""
+        assert self.loss_scaler is not None, "loss scaling is off"
+        return self.loss_scaler.skipped_steps()
+
+    def _bind_loss_scaler(self, lib, st, device, steps_taken: int) -> int:
+        """Registers the scaler's device block for the calls that follow (0: scaling off).  The caller resets it with
+        coot_step_set_loss_scaler(None) behind the step's calls (the registration is thread-local and must not reach the per-op route)."""
+        sc = self.loss_scaler
+        if sc is None:
+            return 0
+        self._det_overflow_guard(True)
+        ptr = sc._ensure(device, steps_taken).data_ptr()
+        _lib.check(lib.coot_step_set_loss_scaler(ptr), "coot_step_set_loss_scaler")
+        return ptr
+
+    def _det_overflow_guard(self, on: bool) -> None:
+        """Deterministic mode under loss scaling: a scaled gradient word can pass the fixed-point range (+-2^23 in scaled units); with the
+        library's overflow guard on such a word becomes NaN, which the scaler's check turns into a skipped step (csrc/det.h).  Process-wide;
+        switching it synchronises the device, so it is switched only when it changes (never inside a capture: the first step of a
+        scaled trainer runs eagerly)."""
+        want = 1 if (on and getattr(self, "deterministic", False)) else 0
+        lib, v = _lib.load(), C.c_int(0)
+        _lib.check(lib.coot_get_option(b"det_overflow_check", C.byref(v)), "coot_get_option")
+        if v.value != want:
+            _lib.check(lib.coot_set_option(b"det_overflow_check", want), "coot_set_option")
+
     # ---- deterministic mode (include/coot_hip.h: coot_det_configure; tests_nntrainer/integration_deter.py:18-66) -----------------
     def set_deterministic(self, on: bool = True) -> None:
         """Run-to-run determinism of the training step: the few fp32 atomic accumulations of the library (bias / LayerNorm parameter
@@ -532,7 +678,8 @@ class RetrievalTrainer:
             self._drop_graphs()  # captured steps carry the mode they were captured in (flush nodes, the shadow's address)
         self.deterministic = bool(on)
         if not on:
-            loss_fn.set_det_loss_word(None)  # (module-global in loss_fn: must not outlive the mode it belongs to)
+            loss_fn.set_det_loss_word(None)
+            self._det_overflow_guard(False)  # (module-global in loss_fn: must not outlive the mode it belongs to)
         if not on and getattr(self, "_det_key", None) is not None:
             torch.cuda.synchronize()  # (no launch of any stream may still add into — or flush — the shadow that is freed below)
             _lib.check(_lib.load().coot_det_configure(0, None, None, None, 0, torch.cuda.current_stream().cuda_stream), "coot_det_configure")
@@ -618,8 +765,14 @@ class RetrievalTrainer:
         if self.lr_scheduler is not None:  # the reference's second key (nntrainer/trainer_base.py:251-261: get_opt_state)
             out["lr_scheduler"] = self.lr_scheduler.state_dict()
         st = getattr(self, "_native", None)
+        sc = self.loss_scaler
+        if sc is not None:  # (under loss scaling the device counts the optimizer steps: a skipped step does not count)
+            out["loss_scaler"] = sc.state_dict()
         if st is not None:
-            out["native"] = {"step": int(st.step), "m": [t.detach().cpu().clone() for t in st.m], "v": [t.detach().cpu().clone() for t in st.v]}
+            step = int(st.step)
+            if sc is not None and sc.block is not None:
+                step = int(out["loss_scaler"]["step"])
+            out["native"] = {"step": step, "m": [t.detach().cpu().clone() for t in st.m], "v": [t.detach().cpu().clone() for t in st.v]}
         return out
 
     def load_optimizer_state_dict(self, state: Dict[str, Any], batch_for_setup: Optional[RetrievalDataBatchTuple] = None) -> None:
@@ -631,6 +784,16 @@ class RetrievalTrainer:
             self.lr_scheduler.load_state_dict(state["lr_scheduler"])
         self.total_step = int(state.get("total_step", self.total_step))
         nat = state.get("native")
+        if state.get("loss_scaler") is not None:
+            if self.loss_scaler is None:
+                self.loss_scaler = LossScaler()
+            self._drop_graphs()
+            ls = dict(state["loss_scaler"])
+            if nat is not None:
+                ls["step"] = int(nat["step"])
+            self.loss_scaler.load_state_dict(ls)
+        elif self.loss_scaler is not None and nat is not None:
+            self.loss_scaler.load_state_dict(dict(self.loss_scaler.state_dict(), step=int(nat["step"])))
         if nat is None:
             # a state the REFERENCE wrote (optimizer_<epoch>.pth = {"optimizer", "lr_scheduler"}, nntrainer/trainer_base.py:251-261) or one
             # of this trainer's autograd route: the native step keeps its moments outside torch.optim, so they are seeded from the torch
@@ -703,7 +866,10 @@ class RetrievalTrainer:
         # deterministic mode: configured here, BEFORE any capture (a reconfiguration drops every cached graph, _det_sync); the key carries
         # the mode and its configuration epoch, so a graph captured under another one is never replayed
         self._det_sync([n._grad_flat for n in st.nets] + [st.losses])
-        key = (st.dims_key, ptrs, st.ws.data_ptr(), self._det_state())
+        sc_block = self.loss_scaler._ensure(batch.vid_feat.device, st.step) if self.loss_scaler is not None else None
+        if sc_block is not None:
+            self._det_overflow_guard(True)  # (outside any capture: switching it synchronises)
+        key = (st.dims_key, ptrs, st.ws.data_ptr(), self._det_state(), sc_block.data_ptr() if sc_block is not None else 0)
         graphs = st.__dict__.setdefault("graphs", {})
         g = graphs.get(key)
         if g is None:
@@ -731,6 +897,8 @@ class RetrievalTrainer:
             g.flags = flags
 
             lib.coot_step_set_device_state(g.state.data_ptr())
+            if sc_block is not None:  # (the replays read and write the same block)
+                lib.coot_step_set_loss_scaler(sc_block.data_ptr())
             try:
                 g.graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g.graph):
@@ -740,6 +908,7 @@ class RetrievalTrainer:
                                                    st.streams[1].cuda_stream), "coot_train_step (capture)")
             finally:
                 lib.coot_step_set_device_state(None)
+                lib.coot_step_set_loss_scaler(None)
             graphs[key] = g
         if not all(n.pack_is_fresh() for n in st.nets):
             return None
@@ -802,7 +971,10 @@ class RetrievalTrainer:
         reference's LR schedulers keep working.
         next_batch: the batch of the FOLLOWING step, if the data loader already has it on the device (lookahead of one): its
         parameter-free input LayerNorm runs inside this step, next to the global networks, instead of at the head of the next one
-        (COOT_STEP_INPUT_STAGES; same results).  Pass the same object to the next call."""
+        (COOT_STEP_INPUT_STAGES; same results).  Pass the same object to the next call.
+        With loss scaling on (self.loss_scaler: enable_loss_scaling) the step seeds scaled loss gradients, unscales the gradient arenas
+        behind the backward and skips the update of all four networks when one of them is not finite (LossScaler); the gradient
+        arenas hold unscaled gradients afterwards, with do_optimizer=False too."""
         lib = _lib.load()
         if getattr(self, "dp", None) is not None:
             return self._train_step_native_dp(batch, do_optimizer, seed, vid_counts, clip_counts, cc_indices, next_batch, defer_join)
@@ -815,6 +987,7 @@ class RetrievalTrainer:
         st, x = self._native_setup(batch)
         if self.optimizer is not None:
             st.cfg.lr = float(self.optimizer.param_groups[0]["lr"])
+        steps_taken = st.step
         if do_optimizer:
             st.step += 1
         if seed is None:
@@ -837,15 +1010,20 @@ class RetrievalTrainer:
             st.join_pending = False  # this call ends with the text stream joined into the current one
         if cc_indices is not None:  # a given draw of the cycle-consistency positions ([2B] int64: clips, then sentences)
             assert cc_indices.dtype == torch.int64 and cc_indices.is_cuda and cc_indices.numel() == 2 * st.dims.B
-            lib.coot_step_set_cycle_indices(cc_indices.data_ptr())
-        self._det_sync([n._grad_flat for n in st.nets] + [st.losses])  # (deterministic mode: the step flushes these ranges itself)
+        # (every thread-local registration below is withdrawn by the finally, whatever raises between them)
         try:
+            if cc_indices is not None:
+                lib.coot_step_set_cycle_indices(cc_indices.data_ptr())
+            self._det_sync([n._grad_flat for n in st.nets] + [st.losses])  # (deterministic mode: the step flushes these ranges itself)
+            self._bind_loss_scaler(lib, st, st.ws.device, steps_taken)
             _lib.check(lib.coot_train_step(C.byref(st.cfg), C.byref(st.bufs), C.byref(x), C.byref(st.dims), st.losses.data_ptr(),
                                            st.ws.data_ptr(), st.ws.numel(), train, int(seed), max(st.step, 1), flags,
                                            main.cuda_stream, main.cuda_stream, st.streams[1].cuda_stream), "coot_train_step")
         finally:
             if cc_indices is not None:
                 lib.coot_step_set_cycle_indices(None)
+            if self.loss_scaler is not None:
+                lib.coot_step_set_loss_scaler(None)
         if do_optimizer:  # the library rebuilt the bf16 packs right after its Adam update
             for n in st.nets:
                 n.mark_packed()
@@ -854,6 +1032,18 @@ class RetrievalTrainer:
 
     def _train_step_native_dp(self, batch, do_optimizer=True, seed=None, vid_counts=None, clip_counts=None, cc_indices=None, next_batch=None,
                               defer_join=False):
+        if self.loss_scaler is None:
+            return self._train_step_native_dp_impl(batch, do_optimizer, seed, vid_counts, clip_counts, cc_indices, next_batch, defer_join)
+        if do_optimizer and self.dp_early_global_update:
+            raise RuntimeError("loss scaling: the data-parallel early update of the global networks (COOT_DP_EARLY=1) cannot run — the update "
+                               "is all or nothing behind the non-finite check of all four networks' reduced gradients")
+        try:  # (the loss-gradient calls of the phases read the scale word; the update / unscale runs the check)
+            return self._train_step_native_dp_impl(batch, do_optimizer, seed, vid_counts, clip_counts, cc_indices, next_batch, defer_join)
+        finally:
+            _lib.load().coot_step_set_loss_scaler(None)
+
+    def _train_step_native_dp_impl(self, batch, do_optimizer=True, seed=None, vid_counts=None, clip_counts=None, cc_indices=None,
+                                   next_batch=None, defer_join=False):
         """Data-parallel native step: this rank's videos through coot_step_forward (C, two streams), ONE
         packed all-gather per embedding level over RCCL, the contrastive loss on the full gathered batch (every rank
         keeps the gradient rows of its own videos — no collective for embedding gradients), the per-video
@@ -866,6 +1056,7 @@ class RetrievalTrainer:
         st, x = self._native_setup(batch)
         if self.optimizer is not None:
             st.cfg.lr = float(self.optimizer.param_groups[0]["lr"])
+        self._bind_loss_scaler(lib, st, dev, st.step)
         if do_optimizer:
             st.step += 1
         if seed is None:
@@ -1047,7 +1238,7 @@ class RetrievalTrainer:
         # tail of the step updates the local networks only.  Same rule as the single call: only when the local backward is long enough
         # to hide the two extra launches (kEarlyMinTokens rows on the video side), and not in deterministic mode.
         d = st.dims
-        early = (do_optimizer and self.dp_early_global_update and not getattr(self, "deterministic", False)
+        early = (do_optimizer and self.dp_early_global_update and not getattr(self, "deterministic", False) and self.loss_scaler is None
                  and d.B * d.Lv + d.Nc * d.Lc >= 8192)
         with torch.cuda.stream(st.comm):
             dp.all_reduce_sum(st.g_glob)
@@ -1059,7 +1250,8 @@ class RetrievalTrainer:
             _lib.check(lib.coot_event_wait(st.EV_TEXT, st.comm.cuda_stream), "coot_event_wait")
             dp.all_reduce_sum(st.g_loc_t)
         dp.all_reduce_sum(st.g_loc_v)
-        if do_optimizer and defer_join:
+        scaled = self.loss_scaler is not None  # (the check reads all four reduced arenas on the main stream: no split join)
+        if do_optimizer and defer_join and not scaled:
             # Each side's update waits for ITS buckets only: the video side (this stream) for the global networks' bucket and its own
             # local one, the text side for the communication stream's end.  The text side's backward ends up to 90 us after the video
             # side's (it gets the CUs the video side leaves); with one join of the communication stream into this stream the video
@@ -1076,6 +1268,8 @@ class RetrievalTrainer:
             for n in st.nets:
                 n.mark_packed()
         else:
+            if scaled:  # the reduced gradients unscaled in place, found_inf set (GradScaler.unscale_); no update, no schedule move
+                _lib.check(lib.coot_step_unscale_grads(C.byref(st.cfg), C.byref(st.bufs), main.cuda_stream), "coot_step_unscale_grads")
             torch.add(st.cl_word, st.cc_word, out=st.losses[0:1])
         self.total_step += 1
 

@@ -11,6 +11,9 @@
  * stays the caller's and must outlive the registration:
  *   coot_step_set_device_state(state)         thread-local; read by every later coot_train_step of the thread (and by every
  *                                             replay of a step captured while it was set) until reset with NULL
+ *   coot_step_set_loss_scaler(block)          thread-local; read and written by every later coot_train_step / coot_step_backward /
+ *                                             coot_step_update / coot_step_unscale_grads and loss-gradient call of the thread (and
+ *                                             by every replay of a step captured while it was set) until reset with NULL
  *   coot_step_set_input_stages(s0, s1, n)     thread-local; written / read by steps that carry COOT_STEP_INPUT_STAGES or
  *                                             COOT_FWD_INPUT_STAGES until reset with (NULL, NULL, 0); a reset also forgets which
  *                                             stage holds which batch
@@ -404,6 +407,34 @@ int coot_step_backward(const coot_step_config* cfg, const coot_step_buffers* buf
  * lr when the schedule changes it.  NULL returns to argument-driven steps.  Thread-local. */
 size_t coot_step_device_state_bytes(void);
 int coot_step_set_device_state(void* state);
+/* Dynamic loss scaling (torch.cuda.amp.GradScaler semantics, decided on the device: no host synchronisation per step).  Opt-in: with
+ * no block set (the default) nothing below happens and every call computes what it always did.  The block is caller-owned DEVICE
+ * memory of coot_step_loss_scaler_bytes() bytes (80), laid out as
+ *   { float scale; int32 growth_tracker; int32 found_inf; int32 skipped; float growth_factor; float backoff_factor;
+ *     int32 growth_interval; int32 work (0); int64 step; int32 pad[2]; 32 bytes of optimizer scalars (written by the library) }
+ * The caller initialises it (scale = 65536, growth_factor = 2, backoff_factor = 0.5, growth_interval = 2000 are GradScaler's defaults;
+ * growth_factor = backoff_factor = 1 hold a fixed scale; step = optimizer steps already taken, the rest 0).  While it is set:
+ *   - the loss-gradient launches (coot_contrastive_fwd_bwd*, coot_cyclecons_fwd_bwd, and those inside coot_train_step) multiply the
+ *     gradients they seed by `scale` (read on the device at run time); the loss words stay unscaled.  The backward is linear in the seed,
+ *     so every 16-bit activation gradient is scaled — what lets the IEEE-half build train: its coot_train_step / coot_step_backward run
+ *     only with a block set (coot_net_bwd, the per-op route, still refuses there);
+ *   - behind the backward, one check launch unscales the four gradient arenas in place (gradient * 1 / scale, as GradScaler.unscale_;
+ *     deterministic mode: after folding their fixed-point sums) and sets found_inf = 1 if any word is NaN or Inf.  On an optimizer step
+ *     a one-thread launch then applies torch._amp_update_scale_: found_inf -> scale *= backoff_factor, growth_tracker = 0, skipped += 1;
+ *     else growth_tracker += 1 and at growth_interval scale *= growth_factor (if finite), growth_tracker = 0; a finite step also does
+ *     step += 1 and derives the optimizer scalars from it (the `step` arguments and the device state block's step are then NOT used
+ *     for the update; lr still comes from cfg or the device state block).  With found_inf set the update launches change no parameter
+ *     or moment word — the step is skipped, its loss words are still written;
+ *   - coot_train_step updates the four networks together behind the check (no early update of the global networks); coot_step_update
+ *     runs the check itself on main_stream first (main_stream must be ordered behind every gradient word, e.g. behind the all-reduce)
+ *     and refuses COOT_UPDATE_GLOBAL_ONLY / COOT_UPDATE_SKIP_GLOBAL; coot_train_step without COOT_STEP_OPTIMIZER and
+ *     coot_step_unscale_grads (a data-parallel step without an update) unscale and set found_inf but leave scale, growth_tracker,
+ *     skipped and step alone.
+ * What the caller may read: behind the step in stream order (main_stream after coot_train_step / coot_step_update / coot_step_unscale_grads)
+ * the gradient arenas hold UNSCALED gradients and found_inf, scale, growth_tracker, skipped and step are final for that step. */
+size_t coot_step_loss_scaler_bytes(void);
+int coot_step_set_loss_scaler(void* block);
+int coot_step_unscale_grads(const coot_step_config* cfg, const coot_step_buffers* bufs, coot_stream_t stream);
 /* Data parallel: hipEvent_t handles (or NULL) that coot_step_backward records on the video / text stream as soon as that side's
  * GLOBAL network backward is enqueued — its parameter gradients (networks 1 and 3) are final from there on, so a communication
  * stream can wait on the events and reduce them while the local backward (two thirds of the pass) still runs.  Thread-local,
