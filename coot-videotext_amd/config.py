@@ -136,6 +136,11 @@ class RetrievalConfig:
         config = resolve_same_as(copy.deepcopy(config))
         self.raw = config
         self.train = _Section(config["train"])
+        # train.clip_gradient (nntrainer/trainer_configs.py:111-112): -1 = off, >= 0 = the max norm of the gradient norm / clipping
+        # (RetrievalTrainer: GradClip, report-only as the reference); below -1 is refused, as the reference does
+        cg = config["train"].get("clip_gradient", -1)
+        if not (isinstance(cg, (int, float)) and not isinstance(cg, bool) and cg >= -1):
+            raise ValueError(f"train.clip_gradient {cg!r}: -1 (off) or a max norm >= 0")
         self.val = _Section(config.get("val", {}))
         self.dataset_train = _Section(config.get("dataset_train", {}))
         self.dataset_val = _Section(config.get("dataset_val", config.get("dataset_train", {})))

@@ -531,17 +531,25 @@ __device__ __forceinline__ void opt_update(const OptK& k, float& p, float g, flo
   }
 }
 
-__device__ __forceinline__ void opt_update_range(const OptK& k, float* p, const float* g, float* m, float* v, const float* decay, long i, long n) {
+// kClip: gradient clipping before the update (coot_step_set_grad_clip) — every gradient word is read times coef (torch's
+// grad.mul_(clip_coef_clamped), one fp32 product); the arena itself keeps the unclipped word
+template <bool kClip = false>
+__device__ __forceinline__ void opt_update_range(const OptK& k, float* p, const float* g, float* m, float* v, const float* decay, long i, long n,
+                                                 float coef = 1.f) {
   if (i + 3 < n) {
     f32x4_t pp = *reinterpret_cast<f32x4_t*>(p + i), gg = *reinterpret_cast<const f32x4_t*>(g + i);
     f32x4_t mm = *reinterpret_cast<f32x4_t*>(m + i), vv = *reinterpret_cast<f32x4_t*>(v + i);
     f32x4_t dd = decay ? *reinterpret_cast<const f32x4_t*>(decay + i) : f32x4_t{1.f, 1.f, 1.f, 1.f};
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { float pj = pp[j], mj = mm[j], vj = vv[j]; opt_update(k, pj, gg[j], mj, vj, dd[j]); pp[j] = pj; mm[j] = mj; vv[j] = vj; }
+    for (int j = 0; j < 4; ++j) {
+      float pj = pp[j], mj = mm[j], vj = vv[j];
+      opt_update(k, pj, kClip ? gg[j] * coef : gg[j], mj, vj, dd[j]);
+      pp[j] = pj; mm[j] = mj; vv[j] = vj;
+    }
     if (k.mode != 3) *reinterpret_cast<f32x4_t*>(p + i) = pp;
     *reinterpret_cast<f32x4_t*>(m + i) = mm; *reinterpret_cast<f32x4_t*>(v + i) = vv;
   } else {
-    for (long e = i; e < n; ++e) opt_update(k, p[e], g[e], m[e], v[e], decay ? decay[e] : 1.f);
+    for (long e = i; e < n; ++e) opt_update(k, p[e], kClip ? g[e] * coef : g[e], m[e], v[e], decay ? decay[e] : 1.f);
   }
 }
 
@@ -569,11 +577,134 @@ struct ScalerBlock {
 static_assert(sizeof(ScalerBlock) == 80, "coot_step_loss_scaler_bytes: layout documented in include/coot_hip.h");
 thread_local ScalerBlock* g_scaler = nullptr;
 
-__global__ __launch_bounds__(256) void adam4_kernel(AdamSegs sg, OptK k_arg, const OptK* k_dev, const ScalerBlock* sc) {
-  const OptK k = sc ? sc->k : (k_dev ? *k_dev : k_arg);
+// Gradient clipping (coot_step_set_grad_clip, include/coot_hip.h): the caller's device block — a 32-byte header, then one fp64
+// partial sum of squares per workgroup of adam4_kernel's grid over the four arenas (capacity: written by the caller), then one
+// ticket per group of 64 partials, each on a 128-byte line of its own.
+// gradnorm_kernel / scaler_check_kernel write the partials; the last workgroup to arrive (an integer ticket behind an agent-scope
+// release) sums them in a fixed order and writes norm, coef = min(max_norm / (norm + 1e-6), 1) and the clipped-step count.
+struct ClipHdr {
+  float max_norm; int mode; float norm; float coef;
+  int clipped; unsigned ticket; int capacity; int pad;
+};
+static_assert(sizeof(ClipHdr) == 32, "coot_step_grad_clip_bytes: layout documented in include/coot_hip.h");
+thread_local ClipHdr* g_clip = nullptr;
+thread_local int g_clip_before = 0;  // 1: clip before the update; 0: report the norm only
+
+// the arena of this workgroup in a four-arena grid
+__device__ __forceinline__ int seg_arena(const AdamSegs& sg) {
   int s = 0;
 #pragma unroll
   for (int t = 1; t < 4; ++t) if ((int)blockIdx.x >= sg.blk0[t]) s = t;
+  return s;
+}
+// deterministic mode (g_det_seg): folds the fixed-point sums of arena s's flush segments into this thread's words [i, i + 4)
+// (segments are disjoint: a word is flushed once; a workgroup covers the 1 024 words from blk * 1 024)
+__device__ __forceinline__ void fold_segs(const AdamSegs& sg, int s, int blk, long i, long n) {
+  long long* sh = sg.sh[s];
+  if (!sh) return;
+  const long b0 = (long)blk * 1024, b1 = b0 + 1024;
+  float* g = sg.g[s];
+  for (int q = sg.fseg0[s]; q < sg.fseg0[s + 1]; ++q) {
+    const long lo = sg.flo[q], hi = sg.fhi[q];
+    if (lo >= b1 || hi <= b0) continue;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const long e = i + j;
+      if (e < lo || e >= hi || e >= n) continue;
+      const long long v = sh[e];
+      if (v != 0) { sh[e] = 0; g[e] = det_fold(g[e], v); }
+    }
+  }
+}
+
+// the sum over a 256-thread workgroup in a fixed order (wave butterflies, then the four waves in index order); valid in thread 0
+__device__ __forceinline__ double block_sum256(double x, double* lds4) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = x;
+  __syncthreads();
+  return ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
+}
+// one workgroup's sum of squares -> partial `idx`; the workgroup that arrives last (of `total`) finishes the norm.  The hand-off
+// needs no fence: the partial is stored write-through (a relaxed agent-scope atomic store: global_store sc1) and waited for before
+// any ticket add, and the last workgroup reads every partial with agent-scope (sc1) loads.  Two levels of tickets: the last of each
+// group of kClipGroup workgroups (a counter of its own behind the partials, one per 128-byte line) takes the ticket in the header —
+// ~60 adds on one address instead of one per workgroup.  (Atomics on one line serialise at the memory side: one ticket for ~3 700
+// workgroups took 73 us per launch, the group counters packed in one line 47 us; a release fence per workgroup, an L2 write-back
+// each, 128 us.)
+constexpr int kClipGroup = 64, kClipTicketStride = 32;  // (uint32 words: 128 bytes)
+__host__ __device__ inline int clip_groups(int n) { return (n + kClipGroup - 1) / kClipGroup; }
+__device__ void clip_publish(ClipHdr* c, int idx, int total, double sq, int mode) {
+  __shared__ double lds4[4];
+  __shared__ int last;
+  double* parts = reinterpret_cast<double*>(c + 1);
+  unsigned* group_tickets = reinterpret_cast<unsigned*>(parts + c->capacity);
+  const double s = block_sum256(sq, lds4);
+  if (threadIdx.x == 0) {
+    last = 0;
+    if (total <= c->capacity) {
+      __hip_atomic_store(parts + idx, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const int grp = idx / kClipGroup, members = min(kClipGroup, total - grp * kClipGroup);
+      unsigned* gt = group_tickets + (size_t)grp * kClipTicketStride;
+      const unsigned t = __hip_atomic_fetch_add(gt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (t == (unsigned)members - 1) {
+        __hip_atomic_store(gt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (the group's last add of this launch)
+        const unsigned u = __hip_atomic_fetch_add(&c->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = u == (unsigned)clip_groups(total) - 1;
+      }
+    } else {  // (a block sized for other arenas: nothing is stored, every workgroup takes the header ticket, the last writes a NaN norm)
+      const unsigned u = __hip_atomic_fetch_add(&c->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      last = u == (unsigned)total - 1;
+    }
+  }
+  __syncthreads();
+  if (!last) return;
+  const int m = total <= c->capacity ? total : 0;
+  double acc = 0.0;
+  for (int q = threadIdx.x; q < m; q += 256) acc += __hip_atomic_load(parts + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();  // (lds4 is reused)
+  const double tot = block_sum256(acc, lds4);
+  if (threadIdx.x == 0) {
+    const float norm = total <= c->capacity ? (float)sqrt(tot) : __builtin_nanf("");  // (a block sized for other arenas: no norm)
+    const float q = c->max_norm / (norm + 1e-6f);
+    const float coef = q < 1.f ? q : (q >= 1.f ? 1.f : q);  // torch.clamp(max=1): a NaN stays NaN
+    c->norm = norm; c->coef = coef; c->mode = mode;
+    if (coef < 1.f) c->clipped += 1;
+    __hip_atomic_store(&c->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (a replayed graph starts from 0 again)
+  }
+}
+
+__device__ __forceinline__ double sumsq4(const float* g, long i, long n) {
+  double sq = 0.0;
+  if (i + 3 < n) {
+    const f32x4_t v = *reinterpret_cast<const f32x4_t*>(g + i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sq += (double)v[j] * v[j];
+  } else {
+    for (long e = i; e < n; ++e) sq += (double)g[e] * g[e];
+  }
+  return sq;
+}
+
+// The global L2 norm of the arenas of `sg` (adam4_kernel's geometry), partials from index `base` of `total`: ONE launch over the four
+// arenas, or two (video pair, text pair) on two streams that share the ticket.  Deterministic mode: folds first, as the update would.
+__global__ __launch_bounds__(256) void gradnorm_kernel(AdamSegs sg, ClipHdr* c, int base, int total, int mode) {
+  const int s = seg_arena(sg);
+  const long n = sg.n[s];
+  const int blk = (int)blockIdx.x - sg.blk0[s];
+  const long i = ((long)blk * 256 + threadIdx.x) * 4;
+  double sq = 0.0;
+  if (i < n) {
+    fold_segs(sg, s, blk, i, n);
+    sq = sumsq4(sg.g[s], i, n);
+  }
+  clip_publish(c, base + (int)blockIdx.x, total, sq, mode);
+}
+
+__global__ __launch_bounds__(256) void adam4_kernel(AdamSegs sg, OptK k_arg, const OptK* k_dev, const ScalerBlock* sc, const ClipHdr* clip) {
+  const OptK k = sc ? sc->k : (k_dev ? *k_dev : k_arg);
+  const int s = seg_arena(sg);
   // rider: total = contrastive + cycle-consistency (both final long before any update; was a 1-thread launch in front of the text backward)
   if (sg.losses && blockIdx.x == 0 && threadIdx.x == 0) {
     if (sg.loss_sh)
@@ -588,25 +719,12 @@ __global__ __launch_bounds__(256) void adam4_kernel(AdamSegs sg, OptK k_arg, con
   const int blk = (int)blockIdx.x - sg.blk0[s];
   const long i = ((long)blk * 256 + threadIdx.x) * 4;
   if (i >= n) return;
-  if (long long* sh = sg.sh[s]) {  // (segments are disjoint: a word is flushed once; a workgroup covers 1 024 words)
-    const long b0 = (long)blk * 1024, b1 = b0 + 1024;
-    float* g = sg.g[s];
-    for (int q = sg.fseg0[s]; q < sg.fseg0[s + 1]; ++q) {
-      const long lo = sg.flo[q], hi = sg.fhi[q];
-      if (lo >= b1 || hi <= b0) continue;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const long e = i + j;
-        if (e < lo || e >= hi || e >= n) continue;
-        const long long v = sh[e];
-        if (v != 0) { sh[e] = 0; g[e] = det_fold(g[e], v); }
-      }
-    }
-  }
+  fold_segs(sg, s, blk, i, n);
   // a workgroup = 1 024 consecutive elements: where the caller marked the decay multiplier as 1.0 on all of them (everything but
   // the blocks that touch a bias vector) the mask is not read (coot_step_buffers.decay_block_all)
   const float* decay = (sg.all1[s] && sg.all1[s][blk]) ? nullptr : sg.decay[s];
-  opt_update_range(k, sg.p[s], sg.g[s], sg.m[s], sg.v[s], decay, i, n);
+  if (clip) opt_update_range<true>(k, sg.p[s], sg.g[s], sg.m[s], sg.v[s], decay, i, n, clip->coef);  // (clipping before the update)
+  else opt_update_range(k, sg.p[s], sg.g[s], sg.m[s], sg.v[s], decay, i, n);
 }
 
 // the scalars of the rules above (host, or thread 0 of step_state_kernel); optimizer: 0 = Adam, 1 = RAdam
@@ -647,40 +765,29 @@ __global__ void step_state_kernel(StepState* s, int optimizer, int degen, float 
 // Loss scaling, part 1: GradScaler.unscale_ of the arenas in place + the non-finite check, in adam4_kernel's geometry (a fixed grid:
 // one workgroup per 1 024 words).  Deterministic mode: the fixed-point sums of the words first (the same fold as adam4_kernel's), so the
 // update launch behind it finds nothing to flush.  found: an integer OR (no float atomics; the result does not depend on the order).
-__global__ __launch_bounds__(256) void scaler_check_kernel(AdamSegs sg, ScalerBlock* sc) {
-  int s = 0;
-#pragma unroll
-  for (int t = 1; t < 4; ++t) if ((int)blockIdx.x >= sg.blk0[t]) s = t;
+// Gradient clipping under a scaler (clip non-null): the sum of squares of the UNSCALED words rides on this pass (clip_publish).
+__global__ __launch_bounds__(256) void scaler_check_kernel(AdamSegs sg, ScalerBlock* sc, ClipHdr* clip, int clip_mode) {
+  const int s = seg_arena(sg);
   const long n = sg.n[s];
   const int blk = (int)blockIdx.x - sg.blk0[s];
   const long i = ((long)blk * 256 + threadIdx.x) * 4;
-  if (i >= n) return;
-  float* g = sg.g[s];
-  if (long long* sh = sg.sh[s]) {
-    const long b0 = (long)blk * 1024, b1 = b0 + 1024;
-    for (int q = sg.fseg0[s]; q < sg.fseg0[s + 1]; ++q) {
-      const long lo = sg.flo[q], hi = sg.fhi[q];
-      if (lo >= b1 || hi <= b0) continue;
+  double sq = 0.0;
+  if (i < n) {
+    float* g = sg.g[s];
+    fold_segs(sg, s, blk, i, n);
+    const float inv = 1.f / sc->scale;  // (GradScaler: scale.double().reciprocal().float(); the scale is a power of two in practice)
+    bool bad = false;
+    if (i + 3 < n) {
+      f32x4_t v = *reinterpret_cast<f32x4_t*>(g + i);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const long e = i + j;
-        if (e < lo || e >= hi || e >= n) continue;
-        const long long v = sh[e];
-        if (v != 0) { sh[e] = 0; g[e] = det_fold(g[e], v); }
-      }
+      for (int j = 0; j < 4; ++j) { v[j] *= inv; bad |= !isfinite(v[j]); sq += (double)v[j] * v[j]; }
+      *reinterpret_cast<f32x4_t*>(g + i) = v;
+    } else {
+      for (long e = i; e < n; ++e) { const float v = g[e] * inv; g[e] = v; bad |= !isfinite(v); sq += (double)v * v; }
     }
+    if (bad) atomicOr(&sc->inf_work, 1);
   }
-  const float inv = 1.f / sc->scale;  // (GradScaler: scale.double().reciprocal().float(); the scale is a power of two in practice)
-  bool bad = false;
-  if (i + 3 < n) {
-    f32x4_t v = *reinterpret_cast<f32x4_t*>(g + i);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { v[j] *= inv; bad |= !isfinite(v[j]); }
-    *reinterpret_cast<f32x4_t*>(g + i) = v;
-  } else {
-    for (long e = i; e < n; ++e) { const float v = g[e] * inv; g[e] = v; bad |= !isfinite(v); }
-  }
-  if (bad) atomicOr(&sc->inf_work, 1);
+  if (clip) clip_publish(clip, (int)blockIdx.x, (int)gridDim.x, sq, clip_mode);
 }
 
 // Loss scaling, part 2 (one thread, behind the check): found_inf for the step; on an optimizer step the scale schedule of
@@ -717,7 +824,7 @@ int scaler_check(const coot_step_config& cfg, const coot_step_buffers& b, bool o
   const int nets[4] = {0, 1, 2, 3};
   AdamSegs sg; int blk = 0;
   RUN(build_segs(cfg, b, nets, 4, st, nullptr, true, sg, blk));
-  hipLaunchKernelGGL(scaler_check_kernel, dim3(blk), dim3(256), 0, st, sg, g_scaler);
+  hipLaunchKernelGGL(scaler_check_kernel, dim3(blk), dim3(256), 0, st, sg, g_scaler, g_clip, g_clip_before);  // (+ the gradient norm)
   COOT_CHECK_LAUNCH("scaler_check");
   hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(1), 0, st, g_scaler, optimize ? 1 : 0, cfg.optimizer, cfg.radam_degentosgd, cfg.lr,
                      g_state_dev ? (const float*)&g_state_dev->lr : (const float*)nullptr, cfg.beta1, cfg.beta2, cfg.eps, cfg.weight_decay);
@@ -780,9 +887,32 @@ int adam_nets(const coot_step_config& cfg, const coot_step_buffers& b, const int
   RUN(build_segs(cfg, b, nets, count, st, losses, flush, sg, blk));
   const OptK k = opt_scalars(cfg.optimizer, cfg.radam_degentosgd, cfg.lr, cfg.beta1, cfg.beta2, cfg.eps, cfg.weight_decay, step);
   hipLaunchKernelGGL(adam4_kernel, dim3(blk), dim3(256), 0, st, sg, k, g_state_dev ? (const OptK*)&g_state_dev->k : (const OptK*)nullptr,
-                     (const ScalerBlock*)g_scaler);
+                     (const ScalerBlock*)g_scaler, (const ClipHdr*)(g_clip_before ? g_clip : nullptr));
   COOT_CHECK_LAUNCH("adam4");
   return 0;
+}
+// adam4_kernel's workgroups over arena i (build_segs)
+static int arena_blocks(const coot_step_config& cfg, int i) { return (int)(((long)coot_net_param_numel(&cfg.net[i]) / 4 + 255) / 256); }
+static int clip_partials(const coot_step_config& cfg) {
+  int n = 0;
+  for (int i = 0; i < 4; ++i) n += arena_blocks(cfg, i);
+  return n;
+}
+// gradient norm (gradnorm_kernel) of `count` consecutive arenas from net nets[0] (0: all four, 2: one side's pair) on `st`, behind
+// everything that wrote them; the partials of nets 2, 3 follow those of nets 0, 1, so two launches of the pairs finish ONE norm
+int grad_norm(const coot_step_config& cfg, const coot_step_buffers& b, const int* nets, int count, hipStream_t st) {
+  AdamSegs sg; int blk = 0;
+  RUN(build_segs(cfg, b, nets, count, st, nullptr, true, sg, blk));
+  const int base = nets[0] == 2 ? arena_blocks(cfg, 0) + arena_blocks(cfg, 1) : 0;
+  hipLaunchKernelGGL(gradnorm_kernel, dim3(blk), dim3(256), 0, st, sg, g_clip, base, clip_partials(cfg), g_clip_before);
+  COOT_CHECK_LAUNCH("gradnorm");
+  return 0;
+}
+// report-only: the norm of the final arenas behind each side's update, one launch per side on that side's stream (no new join)
+int grad_norm_sides(const coot_step_config& cfg, const coot_step_buffers& b, hipStream_t sv, hipStream_t st) {
+  const int vnets[2] = {0, 1}, tnets[2] = {2, 3};
+  RUN(grad_norm(cfg, b, vnets, 2, sv));
+  return grad_norm(cfg, b, tnets, 2, st);
 }
 
 // The cycle-consistency loss scores ONE valid position per video and direction (coot/loss_fn.py:306-314).  Normally drawn on the
@@ -917,8 +1047,17 @@ int coot_step_update(const coot_step_config* cfg, const coot_step_buffers* b, in
     // loss scaling: the update is all or nothing, decided over the four arenas in front of it (main_s is ordered behind all of them)
     COOT_REQUIRE((repack & (COOT_UPDATE_GLOBAL_ONLY | COOT_UPDATE_SKIP_GLOBAL)) == 0, "step_update: with a loss scaler the four networks are updated "
                  "together behind the non-finite check — no early update of the global networks (COOT_UPDATE_GLOBAL_ONLY / SKIP_GLOBAL)");
-    RUN(scaler_check(*cfg, *b, true, sm));
+    RUN(scaler_check(*cfg, *b, true, sm));  // (with a clip block: the norm too)
+  } else if (g_clip && g_clip_before) {
+    // clipping before the update: the norm over the four arenas first, on main_s (ordered behind all of them)
+    COOT_REQUIRE((repack & (COOT_UPDATE_GLOBAL_ONLY | COOT_UPDATE_SKIP_GLOBAL)) == 0, "step_update: clipping before the update scales the four "
+                 "networks' gradients by one norm — no early update of the global networks (COOT_UPDATE_GLOBAL_ONLY / SKIP_GLOBAL)");
+    const int all4[4] = {0, 1, 2, 3};
+    RUN(grad_norm(*cfg, *b, all4, 4, sm));
   }
+  // report-only (no scaler): the norm of the final arenas behind the updates, per side (below; not for a GLOBAL_ONLY call: the
+  // SKIP_GLOBAL call of the same step reads all four)
+  const bool report = g_clip && !g_clip_before && !g_scaler;
   if (repack & COOT_UPDATE_GLOBAL_ONLY) {
     // the two GLOBAL networks only, on main_s alone: their gradients are final (and, data parallel, reduced) a whole local backward
     // before the step's end — the caller runs this on its communication stream behind their bucket (as coot_train_step's early update)
@@ -938,6 +1077,7 @@ int coot_step_update(const coot_step_config* cfg, const coot_step_buffers* b, in
   if (do_pack) RUN(pack_nets(*cfg, *b, vnets, per_side, side_v));
   RUN(adam_nets(*cfg, *b, tnets, per_side, step, st));
   if (do_pack) RUN(pack_nets(*cfg, *b, tnets, per_side, side_t));
+  if (report) RUN(grad_norm_sides(*cfg, *b, sv, st));
   RUN(g_hops.hop(4, sv, sm));
   if ((repack & COOT_UPDATE_DEFER_TEXT_JOIN) == 0) RUN(g_hops.hop(5, st, sm));
   return 0;
@@ -1064,7 +1204,9 @@ int coot_train_step(const coot_step_config* cfg, const coot_step_buffers* b, con
   struct DetScope { ~DetScope() { g_det_plan = DetPlan{}; } } det_scope;
   g_det_plan.fold = optimize && g_det_seg; g_det_plan.losses = losses;
   // (loss scaling: no early update — the step is all or nothing, decided behind BOTH sides' backward)
-  const bool early = optimize && (!det_on() || g_det_seg) && !g_state_dev && !g_scaler;
+  // (clipping before the update: the same — one norm over both sides scales every gradient)
+  const bool together = g_scaler || (g_clip && g_clip_before);
+  const bool early = optimize && (!det_on() || g_det_seg) && !g_state_dev && !together;
   const bool early_v = early && (long)d->B * d->Lv + (long)d->Nc * d->Lc >= kEarlyMinTokens;
   const bool early_t = early && (long)d->B * d->Lp + (long)d->Nc * d->Ls >= kEarlyMinTokens;
   struct EarlyScope { ~EarlyScope() { g_early = EarlyUpdate{}; } } early_scope;
@@ -1082,14 +1224,14 @@ int coot_train_step(const coot_step_config* cfg, const coot_step_buffers* b, con
   // side only — all three loss words are readable there on return (on the text side's launch, losses[0] raced with a deferred join)
   // (the cycle-consistency word: 2 B addends, det.h; with g_det_seg its flush rides on the update launch or on the backward's segment flush)
   if (det_on() && !g_det_seg) RUN(det_flush_range(losses, 3 * sizeof(float), sv));
-  if (g_scaler) {
-    // loss scaling: nothing is updated before the text side's gradients are checked too (below)
+  if (together) {
+    // loss scaling / clipping before the update: nothing is updated before the text side's gradients are in too (below)
   } else if (optimize) RUN(adam_nets(*cfg, *b, vnets, early_v ? 1 : 2, step, sv, losses, g_det_plan.fold));  // (early: the global network is being updated already)
   else {
     hipLaunchKernelGGL(loss_total_kernel, dim3(1), dim3(1), 0, sv, losses);
     COOT_CHECK_LAUNCH("loss_total");
   }
-  if (repack && !g_scaler) RUN(pack_nets(*cfg, *b, vnets, early_v ? 1 : 2, side_v));
+  if (repack && !together) RUN(pack_nets(*cfg, *b, vnets, early_v ? 1 : 2, side_v));
   if (early_v) RUN(g_hops.wait(13, sv));
   g_stamps.mark("video: updated", sv);
   if (piped) coot_internal_set_input_stage(SL.xt, SL.pt, 0);
@@ -1099,12 +1241,14 @@ int coot_train_step(const coot_step_config* cfg, const coot_step_buffers* b, con
   (void)coot_net_grads_overwrite(0);
   coot_internal_set_input_stage(nullptr, nullptr, 0);
   RUN(rc_t);
-  if (g_scaler) {
-    // loss scaling: both sides' gradients -> unscale + non-finite check -> the four networks' update (or none), on the video stream;
-    // the text stream is ordered behind it (a deferred join then still orders everything of the step)
+  if (together) {
+    // loss scaling: both sides' gradients -> unscale + non-finite check (+ norm) -> the four networks' update (or none), on the video
+    // stream; clipping alone: the norm in its place.  The text stream is ordered behind it (a deferred join then still orders
+    // everything of the step)
     RUN(g_hops.hop(8, st, sv));
-    RUN(scaler_check(*cfg, *b, optimize, sv));
     const int all4[4] = {0, 1, 2, 3};
+    if (g_scaler) RUN(scaler_check(*cfg, *b, optimize, sv));
+    else RUN(grad_norm(*cfg, *b, all4, 4, sv));
     if (optimize) RUN(adam_nets(*cfg, *b, all4, 4, step, sv, losses, g_det_plan.fold));
     else {
       hipLaunchKernelGGL(loss_total_kernel, dim3(1), dim3(1), 0, sv, losses);
@@ -1114,9 +1258,12 @@ int coot_train_step(const coot_step_config* cfg, const coot_step_buffers* b, con
     g_stamps.mark("video: updated", sv);
     RUN(g_hops.hop(15, sv, st));
   }
-  if (optimize && !g_scaler) RUN(adam_nets(*cfg, *b, tnets, early_t ? 1 : 2, step, st, nullptr, g_det_plan.fold));
-  if (repack && !g_scaler) RUN(pack_nets(*cfg, *b, tnets, early_t ? 1 : 2, side_t));
+  if (optimize && !together) RUN(adam_nets(*cfg, *b, tnets, early_t ? 1 : 2, step, st, nullptr, g_det_plan.fold));
+  if (repack && !together) RUN(pack_nets(*cfg, *b, tnets, early_t ? 1 : 2, side_t));
   if (early_t) RUN(g_hops.wait(14, st));
+  // report-only clipping: the norm of the final arenas, one launch per side behind its update (and behind the early update of its
+  // global network): off the critical path, and the deferred text join stays (the text side's launch goes with the text stream)
+  if (g_clip && !together) RUN(grad_norm_sides(*cfg, *b, sv, st));
   g_stamps.mark("text: updated", st);
   RUN(g_hops.hop(4, sv, sm));
   if ((do_optimizer & COOT_STEP_DEFER_TEXT_JOIN) == 0) RUN(g_hops.hop(5, st, sm));  // else: the caller (or the next step's text side) orders it
@@ -1143,6 +1290,23 @@ int coot_step_unscale_grads(const coot_step_config* cfg, const coot_step_buffers
   RUN(check_cfg(*cfg));
   COOT_REQUIRE(g_scaler, "step_unscale_grads: no loss scaler set (coot_step_set_loss_scaler)");
   return scaler_check(*cfg, *b, false, (hipStream_t)stream);
+}
+size_t coot_step_grad_clip_bytes(const coot_step_config* cfg) {
+  if (!cfg || check_cfg(*cfg)) return 0;
+  const int n = clip_partials(*cfg);
+  return sizeof(ClipHdr) + sizeof(double) * (size_t)n + sizeof(unsigned) * kClipTicketStride * (size_t)clip_groups(n);
+}
+int coot_step_set_grad_clip(void* block, int before_update) {
+  COOT_REQUIRE(before_update == 0 || before_update == 1, "step_set_grad_clip: before_update is 0 (report the norm) or 1 (clip before the update)");
+  g_clip = (ClipHdr*)block;
+  g_clip_before = block ? before_update : 0;
+  return 0;
+}
+int coot_step_grad_norm(const coot_step_config* cfg, const coot_step_buffers* b, coot_stream_t stream) {
+  RUN(check_cfg(*cfg));
+  COOT_REQUIRE(g_clip, "step_grad_norm: no gradient-clip block set (coot_step_set_grad_clip)");
+  const int all4[4] = {0, 1, 2, 3};
+  return grad_norm(*cfg, *b, all4, 4, (hipStream_t)stream);
 }
 size_t coot_step_input_stage_bytes(const coot_step_config* cfg, const coot_step_dims* dims) {
   if (!cfg || !dims) return 0;

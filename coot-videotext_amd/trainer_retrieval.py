@@ -200,6 +200,107 @@ class LossScaler:
             self.load_state_dict(dict(self._read(), step=int(step)))
 
 
+class GradClip:
+    """The total L2 norm of all gradients of the four networks and torch.nn.utils.clip_grad_norm_'s clipping, computed on the device
+    (include/coot_hip.h: coot_step_set_grad_clip): no host synchronisation per step.  The block the library reads and writes holds
+    max_norm (a device word: set_max_norm changes it without recapturing a graph), the last step's norm and coef = min(max_norm /
+    (norm + 1e-6), 1), and the count of steps with coef < 1.
+    before_update=False (report-only, the default and what the reference's ``train.clip_gradient`` does: it clips after
+    optimizer.step(), so the clipped gradients are thrown away): the norm is reported and nothing else changes — parameters, moments,
+    losses and the gradient arenas are bit-identical to a step without a clipper.  before_update=True: the gradients are scaled by
+    coef between backward and the update (the arenas keep the unclipped words; the update reads them times coef).  Under a LossScaler
+    the norm is that of the unscaled gradients (unscale -> clip -> step -> update)."""
+
+    _FMT = "<fiffiIii"  # max_norm, mode, norm, coef, clipped, ticket, capacity, pad (then capacity fp64 partials, group tickets)
+    _HDR = 32
+
+    def __init__(self, max_norm: float, before_update: bool = False):
+        if not (isinstance(max_norm, (int, float)) and math.isfinite(float(max_norm)) and float(max_norm) >= 0.0):
+            raise ValueError(f"GradClip: max_norm must be a finite number >= 0 ({max_norm!r})")
+        self.before_update = bool(before_update)
+        self._host = {"max_norm": float(max_norm), "clipped_steps": 0}
+        self.block: Optional[torch.Tensor] = None  # device block (created by the first step that needs it)
+
+    def _ensure(self, device, nbytes: int = 32) -> torch.Tensor:
+        """The device block, at least `nbytes` long (coot_step_grad_clip_bytes of the step's configuration), carrying the state over."""
+        nbytes = max(int(nbytes), self._HDR)
+        if self.block is None or self.block.device != torch.device(device) or self.block.numel() < nbytes:
+            import struct
+            h = self._host if self.block is None else self._read()
+            cap = (nbytes - self._HDR) // 8  # partials; a 128-byte ticket line per 64 of them follows them
+            while cap > 0 and self._HDR + 8 * cap + 128 * ((cap + 63) // 64) > nbytes:
+                cap -= 1
+            hdr = struct.pack(self._FMT, h["max_norm"], int(self.before_update), float("nan"), float("nan"), h["clipped_steps"], 0, cap, 0)
+            blk = torch.zeros(nbytes, dtype=torch.uint8)
+            blk[:len(hdr)] = torch.frombuffer(bytearray(hdr), dtype=torch.uint8)
+            self.block = blk.to(device)
+        return self.block
+
+    def _read(self) -> Dict[str, Any]:
+        if self.block is None:
+            return dict(self._host, norm=float("nan"), coef=float("nan"))
+        import struct
+        v = struct.unpack(self._FMT, bytes(self.block[:self._HDR].cpu().numpy().tobytes()))
+        return {"max_norm": v[0], "norm": v[2], "coef": v[3], "clipped_steps": v[4]}
+
+    @property
+    def max_norm(self) -> float:
+        return float(self._host["max_norm"])
+
+    def set_max_norm(self, max_norm: float) -> None:
+        """A new max_norm from the next step on (the device word is rewritten in stream order; no graph is recaptured)."""
+        if not (math.isfinite(float(max_norm)) and float(max_norm) >= 0.0):
+            raise ValueError(f"GradClip: max_norm must be a finite number >= 0 ({max_norm!r})")
+        self._host["max_norm"] = float(max_norm)
+        if self.block is not None:
+            self.block[0:4].view(torch.float32).fill_(float(max_norm))
+
+    @property
+    def norm_tensor(self) -> torch.Tensor:
+        """The last step's norm as a 0-d float32 device tensor (a view of the block: no synchronisation; NaN before the first step)."""
+        if self.block is None:
+            return torch.tensor(float("nan"))
+        return self.block[8:12].view(torch.float32).view(())
+
+    @property
+    def coef_tensor(self) -> torch.Tensor:
+        if self.block is None:
+            return torch.tensor(float("nan"))
+        return self.block[12:16].view(torch.float32).view(())
+
+    def norm(self) -> float:
+        """The last step's total gradient norm (synchronises)."""
+        return float(self._read()["norm"])
+
+    def coef(self) -> float:
+        return float(self._read()["coef"])
+
+    def clipped_steps(self) -> int:
+        """Steps whose coef was < 1 (the norm exceeded max_norm) since the clipper was created (synchronises)."""
+        return int(self._read()["clipped_steps"])
+
+    def state_dict(self) -> Dict[str, Any]:
+        h = self._read()
+        return {"max_norm": float(self._host["max_norm"]), "before_update": self.before_update, "clipped_steps": int(h["clipped_steps"])}
+
+    def load_state_dict(self, state: Dict[str, Any]) -> None:
+        mn = float(state["max_norm"])
+        if not (math.isfinite(mn) and mn >= 0.0):
+            raise ValueError(f"GradClip: max_norm must be a finite number >= 0 ({mn!r})")
+        self.before_update = bool(state.get("before_update", self.before_update))
+        self._host = {"max_norm": mn, "clipped_steps": int(state.get("clipped_steps", 0))}
+        if self.block is not None:  # rewritten from the host state, on the same device and at the same size
+            dev, n, self.block = self.block.device, self.block.numel(), None
+            self._ensure(dev, n)
+
+    def _torch_update(self, norm: torch.Tensor, coef: torch.Tensor) -> None:
+        """The per-op route: norm and coef computed by torch, stored where the native routes store theirs (device ops, no sync)."""
+        blk = self._ensure(norm.device)
+        blk[8:12].view(torch.float32).copy_(norm.reshape(1))
+        blk[12:16].view(torch.float32).copy_(coef.reshape(1))
+        blk[16:20].view(torch.int32).add_((coef < 1.0).to(torch.int32).reshape(1))
+
+
 class RetrievalTrainer:
     # data-parallel native step: Adam + weight pack of the global networks on the communication stream behind their gradient bucket
     # (COOT_UPDATE_GLOBAL_ONLY), as coot_train_step does on one GPU.  Built and parity-tested in round 5; with ONE rank it measured 0.5 %
@@ -209,11 +310,18 @@ class RetrievalTrainer:
     dp_early_global_update = os.environ.get("COOT_DP_EARLY", "0") == "1"
     lookahead_min_stage_bytes = 32 << 20  # train_step_native(next_batch=): only batches whose normalised features reach this size
     _stage_owner = None  # id() of the trainer whose input stages the library currently holds (thread-local there; one training thread here)
+    grad_clip: Optional[GradClip] = None  # gradient norm / clipping (GradClip; set per instance by __init__ / enable_grad_clipping)
 
     def __init__(self, cfg: RetrievalConfig, model_mgr: RetrievalModelManager, is_test: bool = False,
-                 world_size: int = 1, loss_scaler: Optional[LossScaler] = None):
+                 world_size: int = 1, loss_scaler: Optional[LossScaler] = None, grad_clip: Optional[GradClip] = None):
         self.cfg = cfg
         self.loss_scaler: Optional[LossScaler] = loss_scaler  # dynamic loss scaling of the native step (None: off)
+        # gradient norm / clipping (None: off).  Without an argument the reference's key: train.clip_gradient > -1 reports the norm
+        # (nntrainer/trainer_base.py:545-554 clips after the optimizer step, which changes no parameter)
+        cg = float(getattr(cfg.train, "clip_gradient", -1))
+        if grad_clip is None and cg > -1:
+            grad_clip = GradClip(cg)
+        self.grad_clip: Optional[GradClip] = grad_clip
         self.model_mgr = model_mgr
         self.loss_cfg = loss_fn.ContrastiveLossConfig.from_section(cfg.train.contrastive_loss_config)
         self.loss_contr = loss_fn.ContrastiveLoss(self.loss_cfg.margin)
@@ -427,11 +535,27 @@ class RetrievalTrainer:
             net.accumulate_into_flat = False
         if dp is not None:
             dp.allreduce_grads(flat_grads, getattr(self, "comm_stream", None))
+        gc = self.grad_clip
+        if gc is not None and gc.before_update:
+            self._torch_clip(flat_grads, gc, apply=True)  # torch.nn.utils.clip_grad_norm_ between backward and the update
         self.optimizer.step()
+        if gc is not None and not gc.before_update:
+            self._torch_clip(flat_grads, gc, apply=False)  # report-only: the gradients are those of the step (Adam does not write them)
         self.model_mgr.mark_weights_dirty()
         if not torch.cuda.is_current_stream_capturing():
             self.total_step += 1
         return loss.detach(), contr_loss.detach(), (cc_loss.detach() if torch.is_tensor(cc_loss) else torch.zeros_like(loss))
+
+    @staticmethod
+    def _torch_clip(flat_grads, gc: "GradClip", apply: bool) -> None:
+        """torch.nn.utils.clip_grad_norm_'s arithmetic (the norm of the per-tensor norms, coef clamped at 1) over the flat gradient
+        arenas; apply: scale them by coef.  norm / coef / clipped count go into the clipper's block."""
+        norm = torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(g, 2.0) for g in flat_grads]), 2.0)
+        coef = torch.clamp(gc._ensure(norm.device)[0:4].view(torch.float32)[0] / (norm + 1e-6), max=1.0)
+        if apply:
+            for g in flat_grads:
+                g.mul_(coef)
+        gc._torch_update(norm, coef)
 
     # ---- native step: the whole optimisation step sequenced inside libcoot_hip.so ---------------------------------
     def _native_setup(self, batch: RetrievalDataBatchTuple):
@@ -668,6 +792,44 @@ class RetrievalTrainer:
         if v.value != want:
             _lib.check(lib.coot_set_option(b"det_overflow_check", want), "coot_set_option")
 
+    # ---- gradient norm and clipping (GradClip; include/coot_hip.h: coot_step_set_grad_clip) ---------------------------------------
+    def enable_grad_clipping(self, clip: Optional[GradClip] = None, max_norm: Optional[float] = None, before_update: bool = False) -> GradClip:
+        """Turns the gradient norm on for every route: ``clip`` or GradClip(max_norm, before_update).  Drops captured graphs (the
+        mode decides the step's sequencing; a new max_norm alone does not need this: GradClip.set_max_norm)."""
+        if clip is None:
+            if max_norm is None:
+                raise ValueError("enable_grad_clipping: a GradClip or max_norm")
+            clip = GradClip(max_norm, before_update)
+        elif max_norm is not None:
+            raise ValueError("enable_grad_clipping: a GradClip or its constructor arguments, not both")
+        self._drop_graphs()
+        self.grad_clip = clip
+        return clip
+
+    def disable_grad_clipping(self) -> None:
+        if self.grad_clip is None:
+            return
+        self._drop_graphs()
+        self.grad_clip = None
+
+    def last_grad_norm(self) -> float:
+        """The last step's total L2 gradient norm (the reference's state.last_grad_norm; synchronises).  0.0 with no clipper bound,
+        as the reference reports with clipping off."""
+        if self.grad_clip is None:
+            return 0.0
+        self.join_streams()
+        torch.cuda.synchronize()
+        return self.grad_clip.norm()
+
+    def _bind_grad_clip(self, lib, st, device) -> int:
+        """Registers the clipper's block for the calls that follow (0: off).  The caller resets it with coot_step_set_grad_clip(None, 0)."""
+        gc = self.grad_clip
+        if gc is None:
+            return 0
+        ptr = gc._ensure(device, int(lib.coot_step_grad_clip_bytes(C.byref(st.cfg)))).data_ptr()
+        _lib.check(lib.coot_step_set_grad_clip(ptr, int(gc.before_update)), "coot_step_set_grad_clip")
+        return ptr
+
     # ---- deterministic mode (include/coot_hip.h: coot_det_configure; tests_nntrainer/integration_deter.py:18-66) -----------------
     def set_deterministic(self, on: bool = True) -> None:
         """Run-to-run determinism of the training step: the few fp32 atomic accumulations of the library (bias / LayerNorm parameter
@@ -768,6 +930,8 @@ class RetrievalTrainer:
         sc = self.loss_scaler
         if sc is not None:  # (under loss scaling the device counts the optimizer steps: a skipped step does not count)
             out["loss_scaler"] = sc.state_dict()
+        if self.grad_clip is not None:
+            out["grad_clip"] = self.grad_clip.state_dict()
         if st is not None:
             step = int(st.step)
             if sc is not None and sc.block is not None:
@@ -784,6 +948,13 @@ class RetrievalTrainer:
             self.lr_scheduler.load_state_dict(state["lr_scheduler"])
         self.total_step = int(state.get("total_step", self.total_step))
         nat = state.get("native")
+        if state.get("grad_clip") is not None:
+            gcs = state["grad_clip"]
+            if self.grad_clip is None:
+                self.grad_clip = GradClip(float(gcs["max_norm"]), bool(gcs.get("before_update", False)))
+            elif bool(gcs.get("before_update", False)) != self.grad_clip.before_update:
+                self._drop_graphs()
+            self.grad_clip.load_state_dict(gcs)
         if state.get("loss_scaler") is not None:
             if self.loss_scaler is None:
                 self.loss_scaler = LossScaler()
@@ -869,7 +1040,10 @@ class RetrievalTrainer:
         sc_block = self.loss_scaler._ensure(batch.vid_feat.device, st.step) if self.loss_scaler is not None else None
         if sc_block is not None:
             self._det_overflow_guard(True)  # (outside any capture: switching it synchronises)
-        key = (st.dims_key, ptrs, st.ws.data_ptr(), self._det_state(), sc_block.data_ptr() if sc_block is not None else 0)
+        gc = self.grad_clip
+        gc_block = gc._ensure(batch.vid_feat.device, int(lib.coot_step_grad_clip_bytes(C.byref(st.cfg)))) if gc is not None else None
+        key = (st.dims_key, ptrs, st.ws.data_ptr(), self._det_state(), sc_block.data_ptr() if sc_block is not None else 0,
+               (gc_block.data_ptr(), gc.before_update) if gc is not None else 0)
         graphs = st.__dict__.setdefault("graphs", {})
         g = graphs.get(key)
         if g is None:
@@ -899,6 +1073,8 @@ class RetrievalTrainer:
             lib.coot_step_set_device_state(g.state.data_ptr())
             if sc_block is not None:  # (the replays read and write the same block)
                 lib.coot_step_set_loss_scaler(sc_block.data_ptr())
+            if gc_block is not None:  # (likewise; max_norm is read from it at replay time)
+                lib.coot_step_set_grad_clip(gc_block.data_ptr(), int(gc.before_update))
             try:
                 g.graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g.graph):
@@ -909,6 +1085,7 @@ class RetrievalTrainer:
             finally:
                 lib.coot_step_set_device_state(None)
                 lib.coot_step_set_loss_scaler(None)
+                lib.coot_step_set_grad_clip(None, 0)
             graphs[key] = g
         if not all(n.pack_is_fresh() for n in st.nets):
             return None
@@ -1016,6 +1193,7 @@ class RetrievalTrainer:
                 lib.coot_step_set_cycle_indices(cc_indices.data_ptr())
             self._det_sync([n._grad_flat for n in st.nets] + [st.losses])  # (deterministic mode: the step flushes these ranges itself)
             self._bind_loss_scaler(lib, st, st.ws.device, steps_taken)
+            self._bind_grad_clip(lib, st, st.ws.device)
             _lib.check(lib.coot_train_step(C.byref(st.cfg), C.byref(st.bufs), C.byref(x), C.byref(st.dims), st.losses.data_ptr(),
                                            st.ws.data_ptr(), st.ws.numel(), train, int(seed), max(st.step, 1), flags,
                                            main.cuda_stream, main.cuda_stream, st.streams[1].cuda_stream), "coot_train_step")
@@ -1024,6 +1202,8 @@ class RetrievalTrainer:
                 lib.coot_step_set_cycle_indices(None)
             if self.loss_scaler is not None:
                 lib.coot_step_set_loss_scaler(None)
+            if self.grad_clip is not None:
+                lib.coot_step_set_grad_clip(None, 0)
         if do_optimizer:  # the library rebuilt the bf16 packs right after its Adam update
             for n in st.nets:
                 n.mark_packed()
@@ -1032,15 +1212,18 @@ class RetrievalTrainer:
 
     def _train_step_native_dp(self, batch, do_optimizer=True, seed=None, vid_counts=None, clip_counts=None, cc_indices=None, next_batch=None,
                               defer_join=False):
-        if self.loss_scaler is None:
+        if self.loss_scaler is None and self.grad_clip is None:
             return self._train_step_native_dp_impl(batch, do_optimizer, seed, vid_counts, clip_counts, cc_indices, next_batch, defer_join)
-        if do_optimizer and self.dp_early_global_update:
+        if do_optimizer and self.dp_early_global_update and self.loss_scaler is not None:
             raise RuntimeError("loss scaling: the data-parallel early update of the global networks (COOT_DP_EARLY=1) cannot run — the update "
                                "is all or nothing behind the non-finite check of all four networks' reduced gradients")
-        try:  # (the loss-gradient calls of the phases read the scale word; the update / unscale runs the check)
+        try:  # (the loss-gradient calls of the phases read the scale word; the update / unscale runs the check; the norm follows the all-reduce)
             return self._train_step_native_dp_impl(batch, do_optimizer, seed, vid_counts, clip_counts, cc_indices, next_batch, defer_join)
         finally:
-            _lib.load().coot_step_set_loss_scaler(None)
+            if self.loss_scaler is not None:
+                _lib.load().coot_step_set_loss_scaler(None)
+            if self.grad_clip is not None:
+                _lib.load().coot_step_set_grad_clip(None, 0)
 
     def _train_step_native_dp_impl(self, batch, do_optimizer=True, seed=None, vid_counts=None, clip_counts=None, cc_indices=None,
                                    next_batch=None, defer_join=False):
@@ -1057,6 +1240,7 @@ class RetrievalTrainer:
         if self.optimizer is not None:
             st.cfg.lr = float(self.optimizer.param_groups[0]["lr"])
         self._bind_loss_scaler(lib, st, dev, st.step)
+        self._bind_grad_clip(lib, st, dev)
         if do_optimizer:
             st.step += 1
         if seed is None:
@@ -1238,8 +1422,9 @@ class RetrievalTrainer:
         # tail of the step updates the local networks only.  Same rule as the single call: only when the local backward is long enough
         # to hide the two extra launches (kEarlyMinTokens rows on the video side), and not in deterministic mode.
         d = st.dims
+        clip_first = self.grad_clip is not None and self.grad_clip.before_update  # (one norm over all four reduced arenas scales every update)
         early = (do_optimizer and self.dp_early_global_update and not getattr(self, "deterministic", False) and self.loss_scaler is None
-                 and d.B * d.Lv + d.Nc * d.Lc >= 8192)
+                 and not clip_first and d.B * d.Lv + d.Nc * d.Lc >= 8192)
         with torch.cuda.stream(st.comm):
             dp.all_reduce_sum(st.g_glob)
             if early:
@@ -1251,7 +1436,7 @@ class RetrievalTrainer:
             dp.all_reduce_sum(st.g_loc_t)
         dp.all_reduce_sum(st.g_loc_v)
         scaled = self.loss_scaler is not None  # (the check reads all four reduced arenas on the main stream: no split join)
-        if do_optimizer and defer_join and not scaled:
+        if do_optimizer and defer_join and not scaled and not clip_first:
             # Each side's update waits for ITS buckets only: the video side (this stream) for the global networks' bucket and its own
             # local one, the text side for the communication stream's end.  The text side's backward ends up to 90 us after the video
             # side's (it gets the CUs the video side leaves); with one join of the communication stream into this stream the video
@@ -1270,6 +1455,8 @@ class RetrievalTrainer:
         else:
             if scaled:  # the reduced gradients unscaled in place, found_inf set (GradScaler.unscale_); no update, no schedule move
                 _lib.check(lib.coot_step_unscale_grads(C.byref(st.cfg), C.byref(st.bufs), main.cuda_stream), "coot_step_unscale_grads")
+            elif self.grad_clip is not None:  # the norm of the reduced gradients (with a scaler it rode on the check above)
+                _lib.check(lib.coot_step_grad_norm(C.byref(st.cfg), C.byref(st.bufs), main.cuda_stream), "coot_step_grad_norm")
             torch.add(st.cl_word, st.cc_word, out=st.losses[0:1])
         self.total_step += 1
 
@@ -1329,11 +1516,14 @@ class RetrievalTrainer:
             self.lr_scheduler = lrs.make_lr_scheduler(self.optimizer, lrs.SchedulerConfig(self.cfg.raw["lr_scheduler"]),
                                                       float(self.cfg.optimizer.lr), self.cfg.train.num_epochs, steps_per_epoch)
         hist: Dict[str, list] = {"epoch": [], "lr": [], "train_loss": [], "val": []}
+        if self.grad_clip is not None:  # {"last", "max"} of the epoch's step norms (accumulated on the device, read once per epoch)
+            hist["grad_norm"] = []
         for _epoch in range(self.current_epoch, self.cfg.train.num_epochs):
             if self.check_early_stop():
                 break
             self.model_mgr.set_all_models_train()
             loss_sum = None
+            norm_max = None
             # native single-GPU steps: a lookahead of one batch (the loader has it on the device while the step runs: DeviceLoader) lets
             # the step run the next batch's input LayerNorm off its critical path (train_step_native(next_batch=))
             # (only with a loader that keeps a batch's tensors alive while the NEXT one is requested: a list of device batches, or
@@ -1344,6 +1534,10 @@ class RetrievalTrainer:
                 out = self.train_step_native(batch, next_batch=nxt) if native else self.train_step(batch)
                 loss = out[0].detach()
                 loss_sum = loss.clone() if loss_sum is None else loss_sum + loss  # device-side: no sync per step
+                if self.grad_clip is not None:
+                    self.join_streams()
+                    nt = self.grad_clip.norm_tensor
+                    norm_max = nt.clone() if norm_max is None else torch.fmax(norm_max, nt)
                 self.lr_scheduler.step()
             do_val, is_best, val = self.check_is_val_epoch(), False, None
             if do_val:
@@ -1360,6 +1554,9 @@ class RetrievalTrainer:
             hist["epoch"].append(self.current_epoch); hist["lr"].append(self.lr_scheduler.current_lr)
             hist["train_loss"].append(float(loss_sum) / max(steps_per_epoch, 1) if loss_sum is not None else float("nan"))
             hist["val"].append(val)
+            if "grad_norm" in hist:
+                hist["grad_norm"].append({"last": float(self.grad_clip.norm_tensor) if norm_max is not None else float("nan"),
+                                          "max": float(norm_max) if norm_max is not None else float("nan")})
             if on_epoch_end is not None:
                 on_epoch_end(self, do_val, is_best, val)
             self.current_epoch += 1

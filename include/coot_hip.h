@@ -14,6 +14,9 @@
  *   coot_step_set_loss_scaler(block)          thread-local; read and written by every later coot_train_step / coot_step_backward /
  *                                             coot_step_update / coot_step_unscale_grads and loss-gradient call of the thread (and
  *                                             by every replay of a step captured while it was set) until reset with NULL
+ *   coot_step_set_grad_clip(block, before)    thread-local; read and written by every later coot_train_step / coot_step_update /
+ *                                             coot_step_unscale_grads / coot_step_grad_norm of the thread (and by every replay of a
+ *                                             step captured while it was set) until reset with (NULL, 0)
  *   coot_step_set_input_stages(s0, s1, n)     thread-local; written / read by steps that carry COOT_STEP_INPUT_STAGES or
  *                                             COOT_FWD_INPUT_STAGES until reset with (NULL, NULL, 0); a reset also forgets which
  *                                             stage holds which batch
@@ -435,6 +438,36 @@ int coot_step_set_device_state(void* state);
 size_t coot_step_loss_scaler_bytes(void);
 int coot_step_set_loss_scaler(void* block);
 int coot_step_unscale_grads(const coot_step_config* cfg, const coot_step_buffers* bufs, coot_stream_t stream);
+/* Gradient norm and clipping (torch.nn.utils.clip_grad_norm_ over all parameters of the four networks, computed on the device: no
+ * host synchronisation per step).  Opt-in: with no block set (the default) nothing below is launched and every call computes what
+ * it always did.  The block is caller-owned DEVICE memory of coot_step_grad_clip_bytes(cfg) bytes: a 32-byte header, one fp64
+ * partial per workgroup of the update's grid over the four arenas (one per 1 024 parameter words) and one ticket per 64 partials,
+ * each on a 128-byte line of its own:
+ *   { float max_norm; int32 mode; float norm; float coef; int32 clipped; uint32 ticket (0); int32 capacity; int32 pad;
+ *     double partials[capacity]; uint32 group_tickets[(capacity + 63) / 64][32] (0) }
+ * The caller initialises max_norm (>= 0; a device word: it may be rewritten between steps, also under graph replay), capacity = the
+ * largest n with 32 + 8 n + 128 ceil(n / 64) <= coot_step_grad_clip_bytes(cfg), and the rest to 0 (the tickets are 0 again after
+ * every launch).  Each norm launch writes norm = ||every gradient word||_2 (summed in
+ * fp64 in a fixed order: the same bits for the same gradients, whatever the workgroup schedule), coef = min(max_norm / (norm +
+ * 1e-6), 1) (a NaN norm gives a NaN coef, as torch's clamp does), mode = the registration's `before_update`, and clipped += 1 when
+ * coef < 1.  A block with a capacity below the grid gets norm = NaN.
+ * coot_step_set_grad_clip(block, before_update):
+ *   before_update = 0, report only (what the reference does: it clips after optimizer.step(), so its clipping moves no parameter):
+ *     the norm of the step's final gradients is taken behind the update, one launch per side on that side's stream (no early update
+ *     is given up, the deferred text join stays); parameters, moments, loss words and gradient arenas are bit-identical to a step
+ *     without a block;
+ *   before_update = 1, clip before the update: the norm is taken in front of the update and the update reads every gradient word
+ *     times coef (the arenas keep the unclipped words).  coot_train_step updates the four networks together behind the norm (no early
+ *     update of the global networks); coot_step_update takes the norm on main_stream first (main_stream must be ordered behind every
+ *     gradient word) and refuses COOT_UPDATE_GLOBAL_ONLY / COOT_UPDATE_SKIP_GLOBAL.
+ *   With a loss scaler set the sum of squares of the UNSCALED words rides on its check launch (no launch of its own; the order is
+ *   torch's AMP recipe: unscale -> clip -> step -> update); a non-finite gradient skips the step, norm is then not finite.
+ * coot_step_grad_norm: the norm and coef of the arenas as they are (deterministic mode: after folding their fixed-point sums), no
+ * update — e.g. a data-parallel step without one.  norm / coef / clipped are final behind the step in stream order: main_stream
+ * after coot_train_step / coot_step_update, after the text stream's join too where that is deferred. */
+size_t coot_step_grad_clip_bytes(const coot_step_config* cfg);
+int coot_step_set_grad_clip(void* block, int before_update);
+int coot_step_grad_norm(const coot_step_config* cfg, const coot_step_buffers* bufs, coot_stream_t stream);
 /* Data parallel: hipEvent_t handles (or NULL) that coot_step_backward records on the video / text stream as soon as that side's
  * GLOBAL network backward is enqueued — its parameter gradients (networks 1 and 3) are final from there on, so a communication
  * stream can wait on the events and reduce them while the local backward (two thirds of the pass) still runs.  Thread-local,
