@@ -24,24 +24,41 @@ constexpr int RT = 64;   // tile: 64 rows of emb1 x 64 rows of emb2
 constexpr int RK = 32;   // k chunk
 constexpr int RP = RK + 1;
 
+// sum x^2 of one row by one wave: the norm of rt_normalize_kernel and of rt_norms_kernel is this sum's sqrtf
+__device__ __forceinline__ float row_sumsq(const float* src, int d, int lane) {
+  float s = 0.f;
+  for (int c = lane; c < d; c += 64) { const float x = src[c]; s += x * x; }
+  return wave_sum(s);
+}
+
 // x / sqrt(sum x^2) per row (coot/trainer_retrieval.py:400-402: no eps), one wave per row; rows [0, N) of a, then of b
 __global__ __launch_bounds__(256) void rt_normalize_kernel(const float* a, const float* b, int N, int d, float* na, float* nb) {
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= 2 * N) return;
   const float* src = row < N ? a + (long)row * d : b + (long)(row - N) * d;
   float* dst = row < N ? na + (long)row * d : nb + (long)(row - N) * d;
-  float s = 0.f;
-  for (int c = lane; c < d; c += 64) { const float x = src[c]; s += x * x; }
-  s = wave_sum(s);
-  const float nrm = sqrtf(s);
+  const float nrm = sqrtf(row_sumsq(src, d, lane));
   for (int c = lane; c < d; c += 64) dst[c] = src[c] / nrm;
 }
 
 // One 64 x 64 tile of d: thread (ty, tx) of a 16 x 16 grid owns the 4 x 4 block rows 4 ty .., columns 4 tx ..
 // acc[r][c] accumulates in k order, chunk by chunk: the same chain for every element in every pass.
+// A has NA rows, B has NB rows.  NORM (the top-K search, which keeps no normalised copy of a 200 000-row gallery): the staged value
+// is x / norm of its row, the division rt_normalize_kernel makes, so the chain sees the same operands as on a normalised copy.
 struct Tile { float acc[4][4]; };
-__device__ __forceinline__ void tile_dot(const float* A, const float* B, int N, int d, int i0, int j0, float (*As)[RP], float (*Bs)[RP], Tile& t) {
+template <bool NORM = false>
+__device__ __forceinline__ void tile_dot(const float* A, const float* B, int NA, int NB, int d, int i0, int j0, float (*As)[RP], float (*Bs)[RP], Tile& t,
+                                         const float* nA = nullptr, const float* nB = nullptr) {
   const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
+  float ra[8], rb[8];  // NORM: the norms of the 8 rows of each operand this thread stages (the same rows in every chunk)
+  if (NORM) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int r = (tid >> 5) + 8 * q;
+      ra[q] = i0 + r < NA ? nA[i0 + r] : 1.f;
+      rb[q] = j0 + r < NB ? nB[j0 + r] : 1.f;
+    }
+  }
 #pragma unroll
   for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -52,8 +69,13 @@ __device__ __forceinline__ void tile_dot(const float* A, const float* B, int N, 
     for (int q = 0; q < 8; ++q) {
       const int e = tid + 256 * q, r = e >> 5, k = e & 31;
       const bool kin = k0 + k < d;
-      As[r][k] = (kin && i0 + r < N) ? A[(long)(i0 + r) * d + k0 + k] : 0.f;
-      Bs[r][k] = (kin && j0 + r < N) ? B[(long)(j0 + r) * d + k0 + k] : 0.f;
+      if (NORM) {
+        As[r][k] = (kin && i0 + r < NA) ? A[(long)(i0 + r) * d + k0 + k] / ra[q] : 0.f;
+        Bs[r][k] = (kin && j0 + r < NB) ? B[(long)(j0 + r) * d + k0 + k] / rb[q] : 0.f;
+      } else {
+        As[r][k] = (kin && i0 + r < NA) ? A[(long)(i0 + r) * d + k0 + k] : 0.f;
+        Bs[r][k] = (kin && j0 + r < NB) ? B[(long)(j0 + r) * d + k0 + k] : 0.f;
+      }
     }
     __syncthreads();
 #pragma unroll 8
@@ -77,7 +99,7 @@ __global__ __launch_bounds__(256) void rt_diag_kernel(const float* A, const floa
   __shared__ float As[RT][RP], Bs[RT][RP];
   const int i0 = blockIdx.x * RT;
   Tile t;
-  tile_dot(A, B, N, d, i0, i0, As, Bs, t);
+  tile_dot(A, B, N, N, d, i0, i0, As, Bs, t);
   const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
   if (ty == tx) {
 #pragma unroll
@@ -95,7 +117,7 @@ __global__ __launch_bounds__(256) void rt_rank_kernel(const float* A, const floa
   const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
   if (tid < RT) { rowc[tid] = 0; colc[tid] = 0; }
   Tile t;
-  tile_dot(A, B, N, d, i0, j0, As, Bs, t);  // ends with a barrier: the counters are zeroed
+  tile_dot(A, B, N, N, d, i0, j0, As, Bs, t);  // ends with a barrier: the counters are zeroed
   float di[4], dj[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) di[r] = i0 + 4 * ty + r < N ? diag[i0 + 4 * ty + r] : 0.f;
@@ -198,7 +220,174 @@ Ws layout(void* base, int N, int d) {
   return w;
 }
 
+// ---- top-K search: M queries against an N-row gallery (coot_retrieval_topk) --------------------------------------------------
+// Row i of the result = the K best columns of row i of d = queries . gallery^T by the total order (score descending, then
+// column descending) = np.argsort(d[i], kind="stable")[::-1][:K]: the tie rule of the ranks above (j > i counts as ahead), so
+// on square input item i sits at position ranks_12[i] of its row.  d is the tile_dot chain and is never stored (unless the
+// caller asks for it): the selection runs on the tile accumulators.
+//
+// An entry is one 64-bit word, (order-preserving image of the score) << 32 | column: "ahead" is one unsigned compare, a strict
+// total order over every bit pattern (NaNs included), so selection and merge cannot depend on who came first.
+//   rt_topk_kernel: workgroup (split s, row tile I) walks its share of the column tiles.  Per row a sorted list of <= K
+//     entries in LDS; an accumulator is compared with the row's K-th entry (after a few tiles almost none passes) and the
+//     ones that pass are appended to the row's candidate buffer (an LDS counter hands out the slot: the buffer's ORDER depends
+//     on the schedule, its content does not).  Then one wave per row folds the candidates into the list by rank: the new
+//     position of an entry is the number of entries ahead of it.
+//   rt_topk_merge_kernel: the S partial lists of a row hold distinct columns, so the final position of an entry is its own
+//     position plus the number of entries ahead of it in the other lists (binary searches).  S = 1 writes the result directly.
+constexpr int TK_MAX = 128;          // K
+constexpr int TK_SMAX = 64;          // column splits
+constexpr int TK_TARGET_WGS = 1024;  // automatic split count: about four workgroups per CU
+int g_rt_topk_splits = 0;            // coot_set_option("rt_topk_splits", n) (tests); 0 = automatic
+
+typedef unsigned long long tk_entry_t;
+__device__ __forceinline__ tk_entry_t tk_pack(float s, int j) {
+  unsigned u = __float_as_uint(s + 0.0f);  // -0 -> +0: equal scores, as numpy compares them
+  u ^= (unsigned)((int)u >> 31) | 0x80000000u;
+  return ((tk_entry_t)u << 32) | (unsigned)j;
+}
+__device__ __forceinline__ float tk_score(tk_entry_t e) {
+  const unsigned u = (unsigned)(e >> 32);
+  return __uint_as_float(u ^ ((u & 0x80000000u) ? 0x80000000u : 0xFFFFFFFFu));
+}
+// number of entries ahead of v in a list sorted best first
+__device__ __forceinline__ int tk_ahead(const tk_entry_t* L, int n, tk_entry_t v) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (L[mid] > v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+size_t tk_lds_bytes(int K) { return (size_t)2 * RT * RP * 4 + (size_t)RT * RT * 8 + (size_t)RT * K * 8 + 2 * RT * 4; }
+
+// grid (S, row tiles); LDS: As | Bs | cand [RT][RT] | list [RT][K] | cnt [RT] | ncand [RT]   (tk_lds_bytes)
+template <bool NORM>
+__global__ __launch_bounds__(256) void rt_topk_kernel(const float* A, const float* B, const float* nA, const float* nB, int M, int N, int d,
+                                                      int K, int tiles_per_split, int S, float* sim, tk_entry_t* part, int* idx_out,
+                                                      float* score_out) {
+  extern __shared__ __attribute__((aligned(16))) char tk_lds[];
+  float (*As)[RP] = (float (*)[RP])tk_lds;
+  float (*Bs)[RP] = (float (*)[RP])(tk_lds + RT * RP * 4);
+  tk_entry_t* cand = (tk_entry_t*)(tk_lds + 2 * RT * RP * 4);
+  tk_entry_t* list = cand + RT * RT;
+  int* cnt = (int*)(list + RT * K);
+  int* ncand = cnt + RT;
+  const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15, wave = tid >> 6, lane = tid & 63;
+  const int i0 = blockIdx.y * RT, nt = (N + RT - 1) / RT;
+  const int t0 = blockIdx.x * tiles_per_split, t1 = min(nt, t0 + tiles_per_split);
+  if (tid < RT) { cnt[tid] = 0; ncand[tid] = 0; }
+  for (int e = tid; e < RT * K; e += 256) list[e] = 0ull;  // 0 = behind every entry: an unfilled slot
+  for (int tj = t0; tj < t1; ++tj) {
+    const int j0 = tj * RT;
+    Tile t;
+    tile_dot<NORM>(A, B, M, N, d, i0, j0, As, Bs, t, nA, nB);  // ends with a barrier: lists and counters of the previous tile are settled
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = 4 * ty + r, i = i0 + row;
+      if (i >= M) continue;
+      const bool full = cnt[row] >= K;
+      const tk_entry_t kth = list[row * K + K - 1];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int j = j0 + 4 * tx + c;
+        if (j >= N) continue;
+        const float s = t.acc[r][c];
+        if (sim) sim[(long)i * N + j] = s;
+        const tk_entry_t e = tk_pack(s, j);
+        if (!full || e > kth) cand[row * RT + atomicAdd(&ncand[row], 1)] = e;  // <= RT columns of this tile per row
+      }
+    }
+    __syncthreads();
+    // fold the candidates in: wave w takes rows w, w + 4, ...; every entry is read before the barrier and placed after it
+    for (int row = wave; row < RT; row += 4) {
+      const int nc = ncand[row], n = cnt[row];
+      tk_entry_t* L = list + row * K;
+      const tk_entry_t* C = cand + row * RT;
+      const bool hc = lane < nc, h0 = lane < n, h1 = lane + 64 < n;
+      tk_entry_t ec = 0ull, e0 = 0ull, e1 = 0ull;
+      int pc = 0, p0 = lane, p1 = lane + 64;
+      if (nc) {
+        if (hc) { ec = C[lane]; pc = tk_ahead(L, n, ec); }
+        if (h0) e0 = L[lane];
+        if (h1) e1 = L[lane + 64];
+        for (int q = 0; q < nc; ++q) {
+          const tk_entry_t v = C[q];
+          pc += v > ec; p0 += v > e0; p1 += v > e1;
+        }
+      }
+      __syncthreads();
+      if (nc) {
+        if (hc && pc < K) L[pc] = ec;
+        if (h0 && p0 < K) L[p0] = e0;
+        if (h1 && p1 < K) L[p1] = e1;
+        if (lane == 0) { cnt[row] = min(K, n + nc); ncand[row] = 0; }
+      }
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < RT * K; e += 256) {
+    const int row = e / K, r = e - row * K, i = i0 + row;
+    if (i >= M) continue;
+    const tk_entry_t v = list[e];
+    if (S == 1) {
+      idx_out[(long)i * K + r] = (int)(unsigned)v;
+      score_out[(long)i * K + r] = tk_score(v);
+    } else {
+      part[((long)i * S + blockIdx.x) * K + r] = v;
+    }
+  }
+}
+
+// one wave per row: part [M][S][K], every list sorted best first, unfilled slots 0 at its end
+__global__ __launch_bounds__(256) void rt_topk_merge_kernel(const tk_entry_t* part, int M, int S, int K, int* idx_out, float* score_out) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const tk_entry_t* P = part + (long)row * S * K;
+  for (int e = lane; e < S * K; e += 64) {
+    const int s = e / K;
+    const tk_entry_t v = P[e];
+    int rank = e - s * K;
+    for (int t = 0; t < S && rank < K; ++t)
+      if (t != s) rank += tk_ahead(P + t * K, K, v);
+    if (rank < K) {  // (an unfilled slot is behind all N >= K real entries)
+      idx_out[(long)row * K + rank] = (int)(unsigned)v;
+      score_out[(long)row * K + rank] = tk_score(v);
+    }
+  }
+}
+
+// sqrt(sum x^2) of every row of a [Ma, d], then of b [Nb, d]: rt_normalize_kernel's divisor
+__global__ __launch_bounds__(256) void rt_norms_kernel(const float* a, int Ma, const float* b, int Nb, int d, float* na, float* nb) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= Ma + Nb) return;
+  const float s = row_sumsq(row < Ma ? a + (long)row * d : b + (long)(row - Ma) * d, d, lane);
+  if (lane == 0) { if (row < Ma) na[row] = sqrtf(s); else nb[row - Ma] = sqrtf(s); }
+}
+
+// column splits and the tiles each one walks: every split has at least one tile
+struct TkSplit { int S, tiles; };
+TkSplit tk_split(int M, int N) {
+  const int mt = (M + RT - 1) / RT, nt = (N + RT - 1) / RT;
+  int S = g_rt_topk_splits > 0 ? g_rt_topk_splits : (TK_TARGET_WGS + mt - 1) / mt;
+  S = S < 1 ? 1 : S; S = S > TK_SMAX ? TK_SMAX : S; S = S > nt ? nt : S;
+  TkSplit r; r.tiles = (nt + S - 1) / S; r.S = (nt + r.tiles - 1) / r.tiles;
+  return r;
+}
+struct TkWs { float *na, *nb; tk_entry_t* part; size_t bytes; };
+TkWs tk_layout(void* base, int M, int N, int K, int S) {
+  TkWs w; size_t off = 0;
+  auto take = [&](size_t n) { char* p = base ? (char*)base + off : nullptr; off += (n + 255) & ~(size_t)255; return (void*)p; };
+  w.na = (float*)take((size_t)M * 4); w.nb = (float*)take((size_t)N * 4);
+  w.part = (tk_entry_t*)take(S > 1 ? (size_t)M * S * K * 8 : 0);
+  w.bytes = off;
+  return w;
+}
+
 }  // namespace
+void set_rt_topk_splits(int n) { g_rt_topk_splits = n; }
+int get_rt_topk_splits() { return g_rt_topk_splits; }
 }  // namespace coot
 
 using namespace coot;
@@ -231,6 +420,40 @@ int coot_retrieval_ranks(const float* emb1, const float* emb2, int N, int d, int
     if (int rc = check_hip(hipMemsetAsync(w.hist, 0, (size_t)2 * N * 4, st), "memset hist")) return rc;
     hipLaunchKernelGGL(rt_metrics_kernel, dim3(2), dim3(1024), 0, st, (const int*)ranks_12, (const int*)ranks_21, N, w.hist, metrics);
     COOT_CHECK_LAUNCH("rt_metrics");
+  }
+  return 0;
+}
+
+size_t coot_retrieval_topk_workspace_bytes(int M, int N, int d, int K) {
+  (void)d;  // no normalised copy is kept: the norms only
+  if (M < 1 || N < 1 || K < 1) return 256;
+  return tk_layout(nullptr, M, N, K, tk_split(M, N).S).bytes + 256;
+}
+
+int coot_retrieval_topk(const float* queries, const float* gallery, int M, int N, int d, int K, int normalize, int32_t* idx_out,
+                        float* score_out, float* sim_out, void* workspace, size_t workspace_bytes, coot_stream_t stream) {
+  COOT_REQUIRE(queries && gallery && idx_out && score_out && workspace, "retrieval_topk: null pointer");
+  COOT_REQUIRE(M >= 1 && N >= 1 && d >= 1 && (M + RT - 1) / RT <= 65535, "retrieval_topk: M = %d, N = %d, d = %d", M, N, d);
+  COOT_REQUIRE(K >= 1 && K <= N && K <= TK_MAX, "retrieval_topk: K = %d is outside 1 .. min(N = %d, %d)", K, N, TK_MAX);
+  hipStream_t st = (hipStream_t)stream;
+  const TkSplit sp = tk_split(M, N);
+  TkWs w = tk_layout(workspace, M, N, K, sp.S);
+  COOT_REQUIRE(w.bytes <= workspace_bytes, "retrieval_topk: workspace too small (%zu < %zu)", workspace_bytes, w.bytes);
+  const dim3 grid(sp.S, (M + RT - 1) / RT);
+  const size_t lds = tk_lds_bytes(K);
+  if (normalize) {
+    hipLaunchKernelGGL(rt_norms_kernel, dim3((M + N + 3) / 4), dim3(256), 0, st, queries, M, gallery, N, d, w.na, w.nb);
+    COOT_CHECK_LAUNCH("rt_norms");
+    hipLaunchKernelGGL(rt_topk_kernel<true>, grid, dim3(256), lds, st, queries, gallery, (const float*)w.na, (const float*)w.nb, M, N, d, K,
+                       sp.tiles, sp.S, sim_out, w.part, (int*)idx_out, score_out);
+  } else {
+    hipLaunchKernelGGL(rt_topk_kernel<false>, grid, dim3(256), lds, st, queries, gallery, (const float*)nullptr, (const float*)nullptr, M, N, d, K,
+                       sp.tiles, sp.S, sim_out, w.part, (int*)idx_out, score_out);
+  }
+  COOT_CHECK_LAUNCH("rt_topk");
+  if (sp.S > 1) {
+    hipLaunchKernelGGL(rt_topk_merge_kernel, dim3((M + 3) / 4), dim3(256), 0, st, (const tk_entry_t*)w.part, M, sp.S, K, (int*)idx_out, score_out);
+    COOT_CHECK_LAUNCH("rt_topk_merge");
   }
   return 0;
 }

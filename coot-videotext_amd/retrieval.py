@@ -4,7 +4,11 @@ fractions; medr = floor(median)+1; meanr = mean+1.
 compute_retrieval / compute_retrieval_cosine: host (numpy) mirror of the reference functions, for CPU tensors.
 compute_retrieval_device: the same results for embeddings that live on the MI355X, computed by libcoot_hip.so
 (coot_retrieval_ranks: normalisation, similarities, both rank vectors and the metric dictionaries in four launches, the
-N x N matrix is never materialised).  No CPU fallback: CUDA tensors in, device kernels or an error."""
+N x N matrix is never materialised).  No CPU fallback: CUDA tensors in, device kernels or an error.
+
+compute_retrieval_topk / retrieval_topk_device: WHICH gallery items a query retrieves (the reference returns top1 only), for M
+queries against N gallery rows, M and N independent: the host mirror on a similarity matrix, and coot_retrieval_topk on the
+device (similarities and selection fused, no M x N matrix)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -33,6 +37,16 @@ def compute_retrieval(emb1: np.ndarray, emb2: np.ndarray):
     return res1, res2, (res1["r1"] + res2["r1"]) / 2
 
 
+def compute_retrieval_topk(sim: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The k best columns of every row of sim [M, N], best first, and their scores: (idx int32 [M, k], scores [M, k]).  Order:
+    score descending, then column descending — a stable ascending argsort reversed, the tie rule of the device ranks (a later
+    index is ahead).  Column 0 is compute_retrieval_cosine's top1 wherever the row maximum is unique."""
+    sim = np.asarray(sim)
+    assert sim.ndim == 2 and 1 <= k <= sim.shape[1], (sim.shape, k)
+    idx = np.argsort(sim, axis=1, kind="stable")[:, ::-1][:, :k]
+    return idx.astype(np.int32), np.take_along_axis(sim, idx, axis=1)
+
+
 def retrieval_ranks_device(emb1, emb2, normalize: bool = False, want_sim: bool = False):
     """emb1, emb2: cuda float32 [N, d].  Returns (ranks_12 int32 [N], ranks_21 int32 [N], metrics float32 [2, 7], sim or None),
     all on the device (no synchronisation)."""
@@ -53,6 +67,30 @@ def retrieval_ranks_device(emb1, emb2, normalize: bool = False, want_sim: bool =
                                         met.data_ptr(), sim.data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(),
                                         torch.cuda.current_stream().cuda_stream), "coot_retrieval_ranks")
     return r12, r21, met, sim
+
+
+def retrieval_topk_device(queries, gallery, k: int, normalize: bool = False, want_sim: bool = False):
+    """queries [M, d], gallery [N, d]: cuda float32.  Returns (idx int32 [M, k], scores float32 [M, k], sim [M, N] or None), all
+    on the device (no synchronisation): compute_retrieval_topk of the fp32 similarities retrieval_ranks_device counts on, without
+    the M x N matrix (want_sim is a testing aid).  1 <= k <= min(N, 128)."""
+    import torch
+    from . import lib as _lib
+    if not (queries.is_cuda and gallery.is_cuda):
+        raise RuntimeError("retrieval_topk_device needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk)")
+    assert queries.dtype == torch.float32 and gallery.dtype == torch.float32 and queries.dim() == 2 and gallery.dim() == 2
+    assert queries.shape[1] == gallery.shape[1], (queries.shape, gallery.shape)
+    queries, gallery = queries.contiguous(), gallery.contiguous()
+    (m, d), n, k = queries.shape, gallery.shape[0], int(k)
+    lib = _lib.load()
+    dev = queries.device
+    ws = torch.empty(lib.coot_retrieval_topk_workspace_bytes(m, n, d, k), dtype=torch.uint8, device=dev)
+    idx = torch.empty(m, max(k, 0), dtype=torch.int32, device=dev)
+    scores = torch.empty(m, max(k, 0), dtype=torch.float32, device=dev)
+    sim = torch.empty(m, n, dtype=torch.float32, device=dev) if want_sim else None
+    _lib.check(lib.coot_retrieval_topk(queries.data_ptr(), gallery.data_ptr(), m, n, d, k, int(normalize), idx.data_ptr(), scores.data_ptr(),
+                                       sim.data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(),
+                                       torch.cuda.current_stream().cuda_stream), "coot_retrieval_topk")
+    return idx, scores, sim
 
 
 def compute_retrieval_device(emb1, emb2, normalize: bool = False):

@@ -22,7 +22,7 @@ from . import loss_fn
 from .config import RetrievalConfig, RetrievalNetworksConst
 from .model_retrieval import (RetrievalDataBatchTuple, RetrievalModelManager, RetrievalPackedBatchTuple, RetrievalTextEmbTuple,
                               RetrievalVisualEmbTuple)
-from .retrieval import compute_retrieval, compute_retrieval_device  # noqa: F401
+from .retrieval import compute_retrieval, compute_retrieval_device, retrieval_topk_device  # noqa: F401
 
 
 class RAdam(torch.optim.Optimizer):
@@ -1563,14 +1563,18 @@ class RetrievalTrainer:
         return hist
 
     @torch.no_grad()
-    def validate_epoch(self, data_loader, val_clips: bool = True, save_embs: bool = False, save_path: Optional[str] = None):
+    def validate_epoch(self, data_loader, val_clips: bool = True, save_embs: bool = False, save_path: Optional[str] = None,
+                       topk: Optional[int] = None):
         """coot/trainer_retrieval.py:312-477 (metric part): eval forward of every batch, both losses, retrieval metrics of
         the collected embeddings; with ``save_embs`` also the embedding export of :404-415 — the dictionary under
         ``out["embeddings"]`` carries exactly the datasets of the reference's ``embeddings_<epoch>.h5`` (``clip_num``,
         ``sent_num`` — written from clip_num there too, :360 —, ``key``, and for each of vid_emb / par_emb / clip_emb /
         sent_emb / vid_context / par_context the L2-normalised rows plus ``<name>_before_norm``); ``save_path`` writes it
         (``.h5`` through h5py when that is importable — the consumers' format, mart/recursive_caption_dataset.py:159-201 —
-        otherwise ``.npz`` with the same keys)."""
+        otherwise ``.npz`` with the same keys).  ``topk=k`` adds ``out["topk"]``: for each direction (``v2p``, ``p2v`` and,
+        with ``val_clips``, ``c2s``, ``s2c``) the pair (indices int32 [n, k], scores float32 [n, k]) of the k items every query
+        retrieves, best first (retrieval.retrieval_topk_device on the same collected embeddings); ``None``: the dictionary is
+        exactly the one without the option."""
         self.join_streams()
         self.model_mgr.set_all_models_eval()
         keys = ["vid_emb", "par_emb", "clip_emb", "sent_emb"] + (["vid_context", "par_context"] if save_embs else [])
@@ -1598,6 +1602,12 @@ class RetrievalTrainer:
             c2s, s2c, cs_sum = compute_retrieval_device(data["clip_emb"], data["sent_emb"], normalize=True)
             out.update({"c2s": c2s, "s2c": s2c, "val_clip_sent_score_at_1": cs_sum})
         out["loss"] = float(torch.stack(losses).mean())
+        if topk is not None:
+            pairs = [("v2p", "vid_emb", "par_emb"), ("p2v", "par_emb", "vid_emb")]
+            if val_clips:
+                pairs += [("c2s", "clip_emb", "sent_emb"), ("s2c", "sent_emb", "clip_emb")]
+            found = {name: retrieval_topk_device(data[q], data[g], topk, normalize=True)[:2] for name, q, g in pairs}
+            out["topk"] = {name: (i.cpu().numpy(), s.cpu().numpy()) for name, (i, s) in found.items()}  # one D2H copy per array
         if save_embs:
             clip_num = torch.cat(save_clip_num).cpu().numpy()
             emb: Dict[str, Any] = {"clip_num": clip_num, "sent_num": clip_num.copy(), "key": list(save_key)}

@@ -317,6 +317,26 @@ size_t coot_retrieval_workspace_bytes(int N, int d);
 int coot_retrieval_ranks(const float* emb1, const float* emb2, int N, int d, int normalize, int32_t* ranks_12, int32_t* ranks_21,
                          float* metrics, float* sim_out, void* workspace, size_t workspace_bytes, coot_stream_t stream);
 
+/* ---- top-K retrieval search on the device: M queries against an N-row gallery ------------------------------------------
+ * What the model is trained for, for sets that need not be square or aligned (exported embeddings, a few text queries against
+ * every clip): row i of idx_out / score_out [M, K] holds the K best gallery rows for query i and their similarities, best first,
+ * by the total order (similarity descending, then gallery index descending) = np.argsort(s[i], kind="stable")[::-1][:K].
+ *   normalize != 0: every row of both sets is first divided by sqrt(sum x^2), no eps (as in coot_retrieval_ranks);
+ *   s = queries . gallery^T is the fp32 FMA chain of coot_retrieval_ranks (k order, chunks of 32): for M = N the optional
+ *   sim_out [M, N] (testing aid) equals that call's sim_out bit for bit, idx_out[i, r] == i exactly when ranks_12[i] == r
+ *   (r < K: the same tie rule, a later index is ahead), and idx_out[:, 0] is the reference's top1 (nntrainer/retrieval.py:79-98)
+ *   wherever the row maximum is unique;
+ *   1 <= K <= min(N, 128); M, N >= 1, independent, any size.
+ * No M x N array exists unless sim_out is given: the selection runs on the tile accumulators, the column range is split over
+ * workgroups and the per-row partial lists are merged in a second launch.  Every comparison is on the total order above, so the
+ * result does not depend on the split count or on the workgroup schedule (coot_set_option("rt_topk_splits", n) fixes the number
+ * of column splits for tests, 0 = automatic; set it before asking for the workspace size).  A row with non-finite similarities
+ * has unspecified order.  workspace: coot_retrieval_topk_workspace_bytes(M, N, d, K) = the row norms and the partial lists,
+ * (M + N) floats + M x splits x K 64-bit words, splits <= 64. */
+size_t coot_retrieval_topk_workspace_bytes(int M, int N, int d, int K);
+int coot_retrieval_topk(const float* queries, const float* gallery, int M, int N, int d, int K, int normalize, int32_t* idx_out,
+                        float* score_out, float* sim_out, void* workspace, size_t workspace_bytes, coot_stream_t stream);
+
 /* ---- the whole training step as native code (coot/trainer_retrieval.py:253-291) -------------------------------
  * Networks are indexed 0 = net_video_local, 1 = net_video_global, 2 = net_text_local, 3 = net_text_global
  * (coot/configs_retrieval.py:182-189).  All buffers are caller-owned device memory. */
