@@ -109,18 +109,23 @@ __global__ __launch_bounds__(256) void rt_diag_kernel(const float* A, const floa
 }
 
 // pass 2: every tile; row counts -> ranks_ab (emb1 -> emb2), column counts -> ranks_ba
+// PART (coot_retrieval_ranks_part): the rows [row0, row0 + rows) of d only, grid.y = the strip's row tiles, which start at row0
+// (not tile aligned: an element's chain does not depend on the tile it sits in).  Row counts of the strip are final, column
+// counts are the strip's share; sim is the strip [rows, N].  Integer sums, so the strips of a partition add up to the whole.
+template <bool PART>
 __global__ __launch_bounds__(256) void rt_rank_kernel(const float* A, const float* B, int N, int d, const float* diag, float* sim,
-                                                      int* ranks_ab, int* ranks_ba) {
+                                                      int* ranks_ab, int* ranks_ba, int row0, int rows) {
   __shared__ float As[RT][RP], Bs[RT][RP];
   __shared__ int rowc[RT], colc[RT];
-  const int i0 = blockIdx.y * RT, j0 = blockIdx.x * RT;
+  const int r0 = PART ? row0 : 0, r1 = PART ? row0 + rows : N;  // the rows this launch covers
+  const int i0 = r0 + blockIdx.y * RT, j0 = blockIdx.x * RT;
   const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
   if (tid < RT) { rowc[tid] = 0; colc[tid] = 0; }
   Tile t;
-  tile_dot(A, B, N, N, d, i0, j0, As, Bs, t);  // ends with a barrier: the counters are zeroed
+  tile_dot(A, B, r1, N, d, i0, j0, As, Bs, t);  // ends with a barrier: the counters are zeroed
   float di[4], dj[4];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) di[r] = i0 + 4 * ty + r < N ? diag[i0 + 4 * ty + r] : 0.f;
+  for (int r = 0; r < 4; ++r) di[r] = i0 + 4 * ty + r < r1 ? diag[i0 + 4 * ty + r] : 0.f;
 #pragma unroll
   for (int c = 0; c < 4; ++c) dj[c] = j0 + 4 * tx + c < N ? diag[j0 + 4 * tx + c] : 0.f;
   int rc[4] = {0, 0, 0, 0}, cc[4] = {0, 0, 0, 0};
@@ -129,9 +134,9 @@ __global__ __launch_bounds__(256) void rt_rank_kernel(const float* A, const floa
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const int i = i0 + 4 * ty + r, j = j0 + 4 * tx + c;
-      if (i < N && j < N) {
+      if (i < r1 && j < N) {
         const float s = t.acc[r][c];
-        if (sim) sim[(long)i * N + j] = s;
+        if (sim) sim[(long)(i - r0) * N + j] = s;
         if (i != j) {
           // row i of d: is j ahead of i?   column j of d (= row j of d^T): is i ahead of j?
           if (s > di[r] || (s == di[r] && j > i)) ++rc[r];
@@ -145,7 +150,7 @@ __global__ __launch_bounds__(256) void rt_rank_kernel(const float* A, const floa
   for (int c = 0; c < 4; ++c) if (cc[c]) atomicAdd(&colc[4 * tx + c], cc[c]);
   __syncthreads();
   if (tid < RT) {
-    if (i0 + tid < N && rowc[tid]) atomicAdd(ranks_ab + i0 + tid, rowc[tid]);
+    if (i0 + tid < r1 && rowc[tid]) atomicAdd(ranks_ab + i0 + tid, rowc[tid]);
     if (j0 + tid < N && colc[tid]) atomicAdd(ranks_ba + j0 + tid, colc[tid]);
   }
 }
@@ -169,7 +174,7 @@ __global__ __launch_bounds__(1024) void rt_metrics_kernel(const int* ranks_ab, c
     const int r = ranks[i];
     ls += (unsigned long long)r;
     lc[0] += r < 1; lc[1] += r < 5; lc[2] += r < 10; lc[3] += r < 50;
-    atomicAdd(h + r, 1);
+    if ((unsigned)r < (unsigned)N) atomicAdd(h + r, 1);  // (a rank is < N; coot_retrieval_metrics takes the caller's: never outside hist)
   }
   atomicAdd(&s_sum, ls);
 #pragma unroll
@@ -218,6 +223,14 @@ Ws layout(void* base, int N, int d) {
   w.hist = (int*)take((size_t)2 * N * 4);
   w.bytes = off;
   return w;
+}
+
+// the histogram zero fill + rt_metrics_kernel: the tail of coot_retrieval_ranks and all of coot_retrieval_metrics
+int launch_metrics(const int32_t* ranks_12, const int32_t* ranks_21, int N, int* hist, float* metrics, hipStream_t st) {
+  if (int rc = check_hip(hipMemsetAsync(hist, 0, (size_t)2 * N * 4, st), "memset hist")) return rc;
+  hipLaunchKernelGGL(rt_metrics_kernel, dim3(2), dim3(1024), 0, st, (const int*)ranks_12, (const int*)ranks_21, N, hist, metrics);
+  COOT_CHECK_LAUNCH("rt_metrics");
+  return 0;
 }
 
 // ---- top-K search: M queries against an N-row gallery (coot_retrieval_topk) --------------------------------------------------
@@ -414,14 +427,47 @@ int coot_retrieval_ranks(const float* emb1, const float* emb2, int N, int d, int
   const int nt = (N + RT - 1) / RT;
   hipLaunchKernelGGL(rt_diag_kernel, dim3(nt), dim3(256), 0, st, A, B, N, d, w.diag);
   COOT_CHECK_LAUNCH("rt_diag");
-  hipLaunchKernelGGL(rt_rank_kernel, dim3(nt, nt), dim3(256), 0, st, A, B, N, d, (const float*)w.diag, sim_out, (int*)ranks_12, (int*)ranks_21);
+  hipLaunchKernelGGL(rt_rank_kernel<false>, dim3(nt, nt), dim3(256), 0, st, A, B, N, d, (const float*)w.diag, sim_out, (int*)ranks_12, (int*)ranks_21, 0, N);
   COOT_CHECK_LAUNCH("rt_rank");
-  if (metrics) {
-    if (int rc = check_hip(hipMemsetAsync(w.hist, 0, (size_t)2 * N * 4, st), "memset hist")) return rc;
-    hipLaunchKernelGGL(rt_metrics_kernel, dim3(2), dim3(1024), 0, st, (const int*)ranks_12, (const int*)ranks_21, N, w.hist, metrics);
-    COOT_CHECK_LAUNCH("rt_metrics");
-  }
+  if (metrics) return launch_metrics(ranks_12, ranks_21, N, w.hist, metrics, st);
   return 0;
+}
+
+size_t coot_retrieval_ranks_part_workspace_bytes(int N, int d) { return layout(nullptr, N, d).bytes + 256; }
+
+int coot_retrieval_ranks_part(const float* emb1, const float* emb2, int N, int d, int normalize, int row0, int rows, int32_t* counts_12,
+                              int32_t* counts_21, float* sim_out, void* workspace, size_t workspace_bytes, coot_stream_t stream) {
+  COOT_REQUIRE(emb1 && emb2 && counts_12 && counts_21 && workspace, "retrieval_part: null pointer");
+  COOT_REQUIRE(N >= 1 && d >= 1, "retrieval_part: N = %d, d = %d", N, d);
+  COOT_REQUIRE(row0 >= 0 && rows >= 0 && row0 <= N && rows <= N - row0, "retrieval_part: rows [%d, %d + %d) are not inside [0, %d)", row0, row0, rows, N);
+  hipStream_t st = (hipStream_t)stream;
+  Ws w = layout(workspace, N, d);
+  COOT_REQUIRE(w.bytes <= workspace_bytes, "retrieval_part: workspace too small (%zu < %zu)", workspace_bytes, w.bytes);
+  if (int rc = check_hip(hipMemsetAsync(counts_12, 0, (size_t)N * 4, st), "memset counts")) return rc;
+  if (int rc = check_hip(hipMemsetAsync(counts_21, 0, (size_t)N * 4, st), "memset counts")) return rc;
+  if (rows == 0) return 0;
+  const float *A = emb1, *B = emb2;
+  if (normalize) {  // every row: all of emb2 is read, and the diagonal below needs all of emb1
+    hipLaunchKernelGGL(rt_normalize_kernel, dim3((2 * N + 3) / 4), dim3(256), 0, st, emb1, emb2, N, d, w.na, w.nb);
+    COOT_CHECK_LAUNCH("rt_normalize");
+    A = w.na; B = w.nb;
+  }
+  const int nt = (N + RT - 1) / RT;
+  hipLaunchKernelGGL(rt_diag_kernel, dim3(nt), dim3(256), 0, st, A, B, N, d, w.diag);  // d_jj of every column
+  COOT_CHECK_LAUNCH("rt_diag");
+  hipLaunchKernelGGL(rt_rank_kernel<true>, dim3(nt, (rows + RT - 1) / RT), dim3(256), 0, st, A, B, N, d, (const float*)w.diag, sim_out,
+                     (int*)counts_12, (int*)counts_21, row0, rows);
+  COOT_CHECK_LAUNCH("rt_rank_part");
+  return 0;
+}
+
+int coot_retrieval_metrics(const int32_t* ranks_12, const int32_t* ranks_21, int N, float* metrics, void* workspace, size_t workspace_bytes,
+                           coot_stream_t stream) {
+  COOT_REQUIRE(ranks_12 && ranks_21 && metrics && workspace, "retrieval_metrics: null pointer");
+  COOT_REQUIRE(N >= 1, "retrieval_metrics: N = %d", N);
+  COOT_REQUIRE((size_t)2 * N * 4 <= workspace_bytes, "retrieval_metrics: workspace too small (%zu < %zu)", workspace_bytes, (size_t)2 * N * 4);
+  COOT_REQUIRE(((uintptr_t)workspace & 3) == 0, "retrieval_metrics: workspace is not 4-byte aligned");
+  return launch_metrics(ranks_12, ranks_21, N, (int*)workspace, metrics, (hipStream_t)stream);
 }
 
 size_t coot_retrieval_topk_workspace_bytes(int M, int N, int d, int K) {

@@ -33,7 +33,16 @@ class DirectRccl:
     Creation is collective and its outcome is AGREED over the torch group: either every rank gets a communicator or none does
     (DataParallelContext then keeps the torch.distributed calls and says so once)."""
 
-    FLOAT32, SUM = 7, 0  # ncclFloat32, ncclSum (rccl.h)
+    FLOAT32, INT32, SUM = 7, 2, 0  # ncclFloat32, ncclInt32, ncclSum (rccl.h)
+
+    @classmethod
+    def datatype(cls, dtype: torch.dtype) -> int:
+        """ncclDataType_t of a tensor the direct route carries: fp32 (the step) and int32 (the rank counts of sharded validation)."""
+        if dtype == torch.float32:
+            return cls.FLOAT32
+        if dtype == torch.int32:
+            return cls.INT32
+        raise TypeError(f"the direct RCCL route carries float32 and int32, not {dtype}")
 
     class UniqueId(C.Structure):
         _fields_ = [("internal", C.c_ubyte * 128)]  # NCCL_UNIQUE_ID_BYTES (c_ubyte: a c_char array reads back cut at the first NUL)
@@ -100,8 +109,8 @@ class DirectRccl:
                                            torch.cuda.current_stream().cuda_stream), "ncclAllGather")
 
     def all_reduce_sum(self, t: torch.Tensor) -> None:
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda
-        self._check(self.lib.ncclAllReduce(t.data_ptr(), t.data_ptr(), t.numel(), self.FLOAT32, self.SUM, self.comm,
+        assert t.is_contiguous() and t.is_cuda
+        self._check(self.lib.ncclAllReduce(t.data_ptr(), t.data_ptr(), t.numel(), self.datatype(t.dtype), self.SUM, self.comm,
                                            torch.cuda.current_stream().cuda_stream), "ncclAllReduce")
 
     def close(self) -> None:
@@ -262,7 +271,9 @@ class DataParallelContext:
             _all_gather_into(recv, send, self.group)
 
     def all_reduce_sum(self, t: torch.Tensor) -> None:
-        """In-place sum over ranks on the current stream."""
+        """In-place sum over ranks on the current stream: fp32 (gradients) or int32 (the rank counts of sharded validation, summed
+        as integers: exact in any order)."""
+        assert t.dtype in (torch.float32, torch.int32), t.dtype
         r = self._direct(t)
         if r is not None:
             r.all_reduce_sum(t)
@@ -270,11 +281,11 @@ class DataParallelContext:
             _all_reduce(t, dist.ReduceOp.SUM, self.group)
 
     def _direct(self, t: torch.Tensor) -> Optional[DirectRccl]:
-        """The direct RCCL communicator for the step's device collectives (backend "nccl", fp32 device tensors), created collectively
+        """The direct RCCL communicator for the step's device collectives (backend "nccl", fp32 / int32 device tensors), created collectively
         at the first one — every rank's first is the step's embedding gather.  COOT_DP_COLLECTIVES=torch keeps torch.distributed's."""
         d = getattr(self, "_rccl", None)
         if d is None:
-            use = (t.is_cuda and t.dtype == torch.float32 and dist.get_backend(self.group) == "nccl"
+            use = (t.is_cuda and t.dtype in (torch.float32, torch.int32) and dist.get_backend(self.group) == "nccl"
                    and os.environ.get("COOT_DP_COLLECTIVES", "direct") != "torch")
             d = self._rccl = DirectRccl(self.group) if use else False
             if d is not False and d.comm is None:

@@ -8,7 +8,11 @@ N x N matrix is never materialised).  No CPU fallback: CUDA tensors
 
 compute_retrieval_topk / retrieval_topk_device: WHICH gallery items a query retrieves (the reference returns top1 only), for M
 queries against N gallery rows, M and N independent: the host mirror on a similarity matrix, and coot_retrieval_topk on the
-device (similarities and selection fused, no M x N matrix)."""
+device (similarities and selection fused, no M x N matrix).
+
+Sharded validation (data-parallel runs): retrieval_ranks_part_device counts one strip of rows, an integer all-reduce of the
+strips is the whole (compute_retrieval_device(dp=...)), retrieval_metrics_device turns rank vectors into the metrics;
+compute_retrieval_counts_part is the host mirror of a strip."""
 from __future__ import annotations
 
 import ctypes as C
@@ -93,10 +97,87 @@ def retrieval_topk_device(queries, gallery, k: int, normalize: bool = False, wan
     return idx, scores, sim
 
 
-def compute_retrieval_device(emb1, emb2, normalize: bool = False):
+def strip_bounds(n: int, world: int, rank: int) -> Tuple[int, int]:
+    """(row0, rows) of rank's strip of n rows: an even split over the ranks, the remainder to the first ranks."""
+    base, rem = divmod(int(n), int(world))
+    return rank * base + min(rank, rem), base + (1 if rank < rem else 0)
+
+
+def compute_retrieval_counts_part(sim: np.ndarray, row0: int, rows: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Host mirror of coot_retrieval_ranks_part on a similarity matrix sim [N, N]: (counts_12, counts_21) int32 [N] of the strip
+    of rows [row0, row0 + rows).  counts_12[i] = the entries of row i ahead of sim[i, i] (strip rows only, 0 elsewhere),
+    counts_21[j] = the strip's entries of column j ahead of sim[j, j]; "ahead" = larger, or equal with a later index (the device
+    tie rule).  Summed over the strips of any partition of [0, N) they are the two rank vectors."""
+    sim = np.asarray(sim)
+    n = sim.shape[0]
+    assert sim.shape == (n, n) and 0 <= row0 and 0 <= rows and row0 + rows <= n, (sim.shape, row0, rows)
+    c12, c21 = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    if rows == 0:
+        return c12, c21
+    diag = np.diagonal(sim)
+    s = sim[row0:row0 + rows]
+    i, j = np.arange(row0, row0 + rows)[:, None], np.arange(n)[None, :]
+    di, dj = diag[row0:row0 + rows, None], diag[None, :]
+    off = i != j
+    c12[row0:row0 + rows] = (off & ((s > di) | ((s == di) & (j > i)))).sum(axis=1)
+    c21[:] = (off & ((s > dj) | ((s == dj) & (i > j)))).sum(axis=0)
+    return c12, c21
+
+
+def retrieval_ranks_part_device(emb1, emb2, row0: int, rows: int, normalize: bool = False, want_sim: bool = False):
+    """One strip of retrieval_ranks_device: the rows [row0, row0 + rows) of emb1 . emb2^T against all N columns.  Returns
+    (counts int32 [2, N], sim [rows, N] or None) on the device: counts[0] holds the final ranks_12 of the strip's rows (0
+    elsewhere), counts[1] the strip's share of every column's ranks_21.  The sums over the strips of any partition of [0, N) are
+    retrieval_ranks_device's rank vectors exactly (coot_retrieval_ranks_part, include/coot_hip.h); rows == 0 gives zeros."""
+    import torch
+    from . import lib as _lib
+    if not (emb1.is_cuda and emb2.is_cuda):
+        raise RuntimeError("retrieval_ranks_part_device needs CUDA tensors (there is no CPU fallback; use compute_retrieval_counts_part)")
+    assert emb1.dtype == torch.float32 and emb2.dtype == torch.float32 and emb1.shape == emb2.shape and emb1.dim() == 2
+    emb1, emb2 = emb1.contiguous(), emb2.contiguous()
+    n, d = emb1.shape
+    row0, rows = int(row0), int(rows)
+    assert 0 <= row0 and 0 <= rows and row0 + rows <= n, (row0, rows, n)
+    lib = _lib.load()
+    ws = torch.empty(lib.coot_retrieval_ranks_part_workspace_bytes(n, d), dtype=torch.uint8, device=emb1.device)
+    counts = torch.empty(2, n, dtype=torch.int32, device=emb1.device)
+    sim = torch.empty(rows, n, dtype=torch.float32, device=emb1.device) if want_sim else None
+    _lib.check(lib.coot_retrieval_ranks_part(emb1.data_ptr(), emb2.data_ptr(), n, d, int(normalize), row0, rows, counts[0].data_ptr(),
+                                             counts[1].data_ptr(), sim.data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(),
+                                             torch.cuda.current_stream().cuda_stream), "coot_retrieval_ranks_part")
+    return counts, sim
+
+
+def retrieval_metrics_device(ranks_12, ranks_21):
+    """The metrics [2, 7] float32 (VALKEYS order, 1 -> 2 then 2 -> 1) of two cuda int32 rank vectors [N] with entries in [0, N):
+    the bits retrieval_ranks_device returns for the same ranks (coot_retrieval_metrics).  On the device, no synchronisation."""
+    import torch
+    from . import lib as _lib
+    if not (ranks_12.is_cuda and ranks_21.is_cuda):
+        raise RuntimeError("retrieval_metrics_device needs CUDA tensors (there is no CPU fallback; use compute_retrieval_cosine)")
+    assert ranks_12.dtype == torch.int32 and ranks_21.dtype == torch.int32 and ranks_12.dim() == 1 and ranks_12.shape == ranks_21.shape
+    ranks_12, ranks_21 = ranks_12.contiguous(), ranks_21.contiguous()
+    n = ranks_12.shape[0]
+    hist = torch.empty(2 * n, dtype=torch.int32, device=ranks_12.device)
+    met = torch.empty(2, 7, dtype=torch.float32, device=ranks_12.device)
+    _lib.check(_lib.load().coot_retrieval_metrics(ranks_12.data_ptr(), ranks_21.data_ptr(), n, met.data_ptr(), hist.data_ptr(), hist.numel() * 4,
+                                                  torch.cuda.current_stream().cuda_stream), "coot_retrieval_metrics")
+    return met
+
+
+def compute_retrieval_device(emb1, emb2, normalize: bool = False, dp=None):
     """Device version of compute_retrieval (nntrainer/retrieval.py:31-65): (res_1to2, res_2to1, sum_at_1) with the
-    reference's dictionary keys.  One 56-byte D2H copy."""
-    _, _, met, _ = retrieval_ranks_device(emb1, emb2, normalize)
+    reference's dictionary keys.  One 56-byte D2H copy.
+    ``dp`` (dist.DataParallelContext) with more than one rank: every rank holds the SAME emb1 / emb2, counts its strip of rows
+    (strip_bounds), ONE integer all-reduce of the [2, N] counts makes the rank vectors, and the metrics kernel runs on them —
+    the same dictionaries, bit for bit, on every rank.  Without one: the single call."""
+    if dp is not None and dp.world > 1:
+        row0, rows = strip_bounds(emb1.shape[0], dp.world, dp.rank)
+        counts, _ = retrieval_ranks_part_device(emb1, emb2, row0, rows, normalize)
+        dp.all_reduce_sum(counts)
+        met = retrieval_metrics_device(counts[0], counts[1])
+    else:
+        _, _, met, _ = retrieval_ranks_device(emb1, emb2, normalize)
     m = met.cpu().numpy().astype(np.float64)
     res1 = {k: float(v) for k, v in zip(VALKEYS, m[0])}
     res2 = {k: float(v) for k, v in zip(VALKEYS, m[1])}

@@ -317,6 +317,27 @@ size_t coot_retrieval_workspace_bytes(int N, int d);
 int coot_retrieval_ranks(const float* emb1, const float* emb2, int N, int d, int normalize, int32_t* ranks_12, int32_t* ranks_21,
                          float* metrics, float* sim_out, void* workspace, size_t workspace_bytes, coot_stream_t stream);
 
+/* ---- the same ranking, one strip of rows at a time (sharded validation: every rank of a data-parallel run takes a strip) ----
+ * coot_retrieval_ranks_part counts on the rows [row0, row0 + rows) of d = emb1 . emb2^T against all N columns.  It zeroes
+ * counts_12 and counts_21 (int32 [N] each) itself, then
+ *   counts_12[i] = ranks_12[i] of coot_retrieval_ranks for row0 <= i < row0 + rows, 0 elsewhere;
+ *   counts_21[j] = the number of rows i of the strip that are ahead of j in column j, for every j;
+ *   sim_out (optional, [rows, N]): the strip of the similarity matrix (testing aid).
+ * Normalisation, the similarity chain, the comparison and the tie rule are those of coot_retrieval_ranks.  row0 and rows are
+ * arbitrary (0 <= row0, 0 <= rows, row0 + rows <= N; not tile aligned); rows == 0 only zeroes the outputs.
+ * STRIP CONTRACT: for any partition of [0, N) into strips, the element-wise integer sums of counts_12 and of counts_21 over the
+ * strips equal ranks_12 and ranks_21 of coot_retrieval_ranks exactly, in any order of summation (an all-reduce of the counts),
+ * and the stacked sim_out strips equal its sim_out bit for bit.
+ * coot_retrieval_metrics computes the 14 metric floats of coot_retrieval_ranks from two rank vectors (e.g. the reduced counts):
+ * the same bits that call writes for the same ranks.  Ranks must lie in [0, N).  Its workspace holds 2 N int32 (4-byte aligned;
+ * a workspace of coot_retrieval_ranks_part_workspace_bytes(N, d) is large enough).
+ * Neither call retains a pointer: every buffer may be freed or reused once the work enqueued on `stream` has completed. */
+size_t coot_retrieval_ranks_part_workspace_bytes(int N, int d);
+int coot_retrieval_ranks_part(const float* emb1, const float* emb2, int N, int d, int normalize, int row0, int rows, int32_t* counts_12,
+                              int32_t* counts_21, float* sim_out, void* workspace, size_t workspace_bytes, coot_stream_t stream);
+int coot_retrieval_metrics(const int32_t* ranks_12, const int32_t* ranks_21, int N, float* metrics, void* workspace, size_t workspace_bytes,
+                           coot_stream_t stream);
+
 /* ---- top-K retrieval search on the device: M queries against an N-row gallery ------------------------------------------
  * What the model is trained for, for sets that need not be square or aligned (exported embeddings, a few text queries against
  * every clip): row i of idx_out / score_out [M, K] holds the K best gallery rows for query i and their similarities, best first,
