@@ -557,7 +557,7 @@ __global__ __launch_bounds__(256) void cl_finish_kernel(ClFinishArgs A) {
 #pragma unroll
   for (int t = 1; t < 6; ++t) if (grow >= A.s[t].row0) si = t;
   const ClSet& S = A.s[si];
-  if (!S.dv) return;
+  if (!S.dv || S.nc == 0) return;  // no term of this set is switched on: nothing to add (and nobody wrote its 1 / norm on the one-launch path)
   const int row = grow - S.row0, d = S.d;
   if (row < S.w0 || row >= S.w0 + S.wn) return;  // data-parallel: a rank keeps the gradient rows of its own videos / clips
   // One memory round trip: every load of the row — the violation counts, the half-term strips, the other set's rows, the raw row and
@@ -697,7 +697,7 @@ int launch_contrastive_fused(const float* const v[6], float* const dv[6], int n_
     COOT_REQUIRE(d_high <= 1024 && d_low <= 1024, "contrastive: embedding dims up to 1024 (%d, %d)", d_high, d_low);
   }
   FBump B(scratch, scratch_bytes); FusedLayout L; layout_fused(n_high, n_low, d_high, d_low, B, L);
-  COOT_REQUIRE(!B.overflow, "contrastive: scratch too small (%zu < %zu)", scratch_bytes, B.off);
+  COOT_REQUIRE(!B.overflow && scratch_bytes >= B.off + 256, "contrastive: scratch too small (%zu < %zu: coot_contrastive_scratch_bytes)", scratch_bytes, B.off + 256);
   const int Ns[3] = {n_high, n_low, n_high}, ds[3] = {d_high, d_low, d_low};
   const bool bwd = dv[0] != nullptr;
   ClNormArgs na; int rows = 0;
