@@ -15,6 +15,6 @@ from .nets import TransformerHip, pack_by_count  # noqa: F401
 from .retrieval import compute_retrieval, compute_retrieval_cosine, compute_retrieval_topk, retrieval_topk_device  # noqa: F401
 from .retrieval import compute_retrieval_counts_part, retrieval_metrics_device, retrieval_ranks_part_device  # noqa: F401
 from .trainer_retrieval import GradClip, LossScaler, RetrievalTrainer, make_optimizer  # noqa: F401
-from .trainer_retrieval import loader_order_permutation, shard_batch_indices  # noqa: F401
+from .validation import loader_order_permutation, save_embeddings, shard_batch_indices  # noqa: F401
 from . import lr_scheduler  # noqa: F401,E402
 from .dataset_retrieval import BatchArena, DeviceLoader, RetrievalDataPointTuple, collate_fn  # noqa: F401,E402

@@ -3,8 +3,8 @@ fractions; medr = floor(median)+1; meanr = mean+1.
 
 compute_retrieval / compute_retrieval_cosine: host (numpy) mirror of the reference functions, for CPU tensors.
 compute_retrieval_device: the same results for embeddings that live on the MI355X, computed by libcoot_hip.so
-(coot_retrieval_ranks: normalisation, similarities, both rank vectors and the metric dictionaries in four launches, the
-N x N matrix is never materialised).  No CPU fallback: CUDA tensors in, device kernels or an error.
+(coot_retrieval_ranks_part + coot_retrieval_metrics: normalisation, similarities, both rank vectors and the metric dictionaries
+in four launches, the N x N matrix is never materialised).  No CPU fallback: CUDA tensors in, device kernels or an error.
 
 compute_retrieval_topk / retrieval_topk_device: WHICH gallery items a query retrieves (the reference returns top1 only), for M
 queries against N gallery rows, M and N independent: the host mirror on a similarity matrix, and coot_retrieval_topk on the
@@ -51,15 +51,22 @@ def compute_retrieval_topk(sim: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndar
     return idx.astype(np.int32), np.take_along_axis(sim, idx, axis=1)
 
 
+def _device_pair(fn: str, host: str, a, b, dtype, same_shape: bool = True, dim: int = 2):
+    """The entry of every *_device wrapper: CUDA tensors or an error naming the host mirror, the dtype and the dimension
+    asserted (and equal shapes, unless only the row width has to agree), contiguous copies returned."""
+    if not (a.is_cuda and b.is_cuda):
+        raise RuntimeError(f"{fn} needs CUDA tensors (there is no CPU fallback; use {host})")
+    assert a.dtype == dtype and b.dtype == dtype and a.dim() == dim and b.dim() == dim, (a.dtype, b.dtype, a.shape, b.shape)
+    assert a.shape == b.shape if same_shape else a.shape[1] == b.shape[1], (a.shape, b.shape)
+    return a.contiguous(), b.contiguous()
+
+
 def retrieval_ranks_device(emb1, emb2, normalize: bool = False, want_sim: bool = False):
     """emb1, emb2: cuda float32 [N, d].  Returns (ranks_12 int32 [N], ranks_21 int32 [N], metrics float32 [2, 7], sim or None),
     all on the device (no synchronisation)."""
     import torch
     from . import lib as _lib
-    if not (emb1.is_cuda and emb2.is_cuda):
-        raise RuntimeError("retrieval_ranks_device needs CUDA tensors (there is no CPU fallback; use compute_retrieval)")
-    assert emb1.dtype == torch.float32 and emb2.dtype == torch.float32 and emb1.shape == emb2.shape and emb1.dim() == 2
-    emb1, emb2 = emb1.contiguous(), emb2.contiguous()
+    emb1, emb2 = _device_pair("retrieval_ranks_device", "compute_retrieval", emb1, emb2, torch.float32)
     n, d = emb1.shape
     lib = _lib.load()
     ws = torch.empty(lib.coot_retrieval_workspace_bytes(n, d), dtype=torch.uint8, device=emb1.device)
@@ -79,11 +86,7 @@ def retrieval_topk_device(queries, gallery, k: int, normalize: bool = False, wan
     the M x N matrix (want_sim is a testing aid).  1 <= k <= min(N, 128)."""
     import torch
     from . import lib as _lib
-    if not (queries.is_cuda and gallery.is_cuda):
-        raise RuntimeError("retrieval_topk_device needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk)")
-    assert queries.dtype == torch.float32 and gallery.dtype == torch.float32 and queries.dim() == 2 and gallery.dim() == 2
-    assert queries.shape[1] == gallery.shape[1], (queries.shape, gallery.shape)
-    queries, gallery = queries.contiguous(), gallery.contiguous()
+    queries, gallery = _device_pair("retrieval_topk_device", "compute_retrieval_topk", queries, gallery, torch.float32, same_shape=False)
     (m, d), n, k = queries.shape, gallery.shape[0], int(k)
     lib = _lib.load()
     dev = queries.device
@@ -131,10 +134,7 @@ def retrieval_ranks_part_device(emb1, emb2, row0: int, rows: int, normalize: boo
     retrieval_ranks_device's rank vectors exactly (coot_retrieval_ranks_part, include/coot_hip.h); rows == 0 gives zeros."""
     import torch
     from . import lib as _lib
-    if not (emb1.is_cuda and emb2.is_cuda):
-        raise RuntimeError("retrieval_ranks_part_device needs CUDA tensors (there is no CPU fallback; use compute_retrieval_counts_part)")
-    assert emb1.dtype == torch.float32 and emb2.dtype == torch.float32 and emb1.shape == emb2.shape and emb1.dim() == 2
-    emb1, emb2 = emb1.contiguous(), emb2.contiguous()
+    emb1, emb2 = _device_pair("retrieval_ranks_part_device", "compute_retrieval_counts_part", emb1, emb2, torch.float32)
     n, d = emb1.shape
     row0, rows = int(row0), int(rows)
     assert 0 <= row0 and 0 <= rows and row0 + rows <= n, (row0, rows, n)
@@ -153,10 +153,7 @@ def retrieval_metrics_device(ranks_12, ranks_21):
     the bits retrieval_ranks_device returns for the same ranks (coot_retrieval_metrics).  On the device, no synchronisation."""
     import torch
     from . import lib as _lib
-    if not (ranks_12.is_cuda and ranks_21.is_cuda):
-        raise RuntimeError("retrieval_metrics_device needs CUDA tensors (there is no CPU fallback; use compute_retrieval_cosine)")
-    assert ranks_12.dtype == torch.int32 and ranks_21.dtype == torch.int32 and ranks_12.dim() == 1 and ranks_12.shape == ranks_21.shape
-    ranks_12, ranks_21 = ranks_12.contiguous(), ranks_21.contiguous()
+    ranks_12, ranks_21 = _device_pair("retrieval_metrics_device", "compute_retrieval_cosine", ranks_12, ranks_21, torch.int32, dim=1)
     n = ranks_12.shape[0]
     hist = torch.empty(2 * n, dtype=torch.int32, device=ranks_12.device)
     met = torch.empty(2, 7, dtype=torch.float32, device=ranks_12.device)
@@ -170,14 +167,13 @@ def compute_retrieval_device(emb1, emb2, normalize: bool = False, dp=None):
     reference's dictionary keys.  One 56-byte D2H copy.
     ``dp`` (dist.DataParallelContext) with more than one rank: every rank holds the SAME emb1 / emb2, counts its strip of rows
     (strip_bounds), ONE integer all-reduce of the [2, N] counts makes the rank vectors, and the metrics kernel runs on them —
-    the same dictionaries, bit for bit, on every rank.  Without one: the single call."""
-    if dp is not None and dp.world > 1:
-        row0, rows = strip_bounds(emb1.shape[0], dp.world, dp.rank)
-        counts, _ = retrieval_ranks_part_device(emb1, emb2, row0, rows, normalize)
+    the same dictionaries, bit for bit, on every rank.  Without one, or with one rank: the strip is all rows and nothing is reduced."""
+    W, R = (dp.world, dp.rank) if dp is not None and dp.world > 1 else (1, 0)
+    row0, rows = strip_bounds(emb1.shape[0], W, R)
+    counts, _ = retrieval_ranks_part_device(emb1, emb2, row0, rows, normalize)
+    if W > 1:
         dp.all_reduce_sum(counts)
-        met = retrieval_metrics_device(counts[0], counts[1])
-    else:
-        _, _, met, _ = retrieval_ranks_device(emb1, emb2, normalize)
+    met = retrieval_metrics_device(counts[0], counts[1])
     m = met.cpu().numpy().astype(np.float64)
     res1 = {k: float(v) for k, v in zip(VALKEYS, m[0])}
     res2 = {k: float(v) for k, v in zip(VALKEYS, m[1])}

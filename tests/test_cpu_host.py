@@ -354,7 +354,7 @@ def test_embedding_export_hdf5_branch_with_a_recording_h5py(tmp_path, monkeypatc
     accepts (numeric ndarrays, a list of str for ``key``) — the file format itself is h5py's business."""
     import sys
     import types
-    from coot_videotext_amd.trainer_retrieval import save_embeddings
+    from coot_videotext_amd.validation import save_embeddings
     written = {}
 
     class _File:

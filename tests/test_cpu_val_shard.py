@@ -155,7 +155,7 @@ def test_counts_part_follows_the_device_tie_rule(cva, n):
 @pytest.mark.parametrize("n", [0, 1, 5, 16])
 @pytest.mark.parametrize("world", [1, 2, 3, 8])
 def test_shards_partition_the_loader_and_the_permutation_restores_it(cva, n, world):
-    from coot_videotext_amd.trainer_retrieval import loader_order_permutation, shard_batch_indices
+    from coot_videotext_amd.validation import loader_order_permutation, shard_batch_indices
     shards = [shard_batch_indices(n, world, r) for r in range(world)]
     assert sorted(b for s in shards for b in s) == list(range(n))
     assert all(s == sorted(s) and all(b % world == r for b in s) for r, s in enumerate(shards))
@@ -186,7 +186,7 @@ def _worker(rank, world, port):
     import coot_videotext_amd  # noqa: F401  (registers the package alias)
     from coot_videotext_amd import dist as cdist
     from coot_videotext_amd.retrieval import compute_retrieval_counts_part, strip_bounds
-    from coot_videotext_amd.trainer_retrieval import gather_in_loader_order, shard_batch_indices
+    from coot_videotext_amd.validation import gather_in_loader_order, shard_batch_indices
     dp = cdist.DataParallelContext()
     # the rank counts: one int32 all-reduce of [2, N] is the whole, as integers
     n = 37

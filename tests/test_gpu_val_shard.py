@@ -182,20 +182,22 @@ def test_replicated_validation_enters_no_collective(env, single, tmp_path):
     with pytest.raises(AssertionError, match="needs a data-parallel context"):
         W.validate(tr, W.loader(), str(tmp_path / "d.npz"), sharded=True)
 
+    class OneRank(_NoCollectives):  # a context of one rank has nothing to shard over: sharded=True reads ``world`` and nothing else
+        world = 1
+
+    tr.dp = OneRank()
+    out = W.flatten(W.validate(tr, W.loader(), str(tmp_path / "e.npz"), sharded=True))
+    assert set(out) == set(single) and all(np.array_equal(out[k], single[k]) for k in single)
+
 
 def test_global_max_hook_is_not_entered_by_sharded_validation(env):
     """The model manager's data-parallel hook (a per-batch collective) is set aside inside the sharded loop and put back."""
-    torch, cva = env
-    from coot_videotext_amd.trainer_retrieval import RetrievalTrainer
     tr = W.trainer()
 
     def hook(v):
         raise AssertionError("global max collective inside the validation loop")
 
-    class OneRankWorld(_NoCollectives):  # the loop runs, the first collective after it raises
-        pass
-
-    tr.dp, tr.model_mgr.global_max_fn = OneRankWorld(), hook
+    tr.dp, tr.model_mgr.global_max_fn = _NoCollectives(), hook  # the loop runs, the first collective after it raises
     with pytest.raises(AssertionError, match="entered a collective: exchange_shapes"):
-        RetrievalTrainer._validate_epoch_sharded(tr, W.loader(), True, False, None, None)
+        tr.validate_epoch(W.loader(), True, False, None, None)
     assert tr.model_mgr.global_max_fn is hook

@@ -3,7 +3,7 @@
     python tests/val_shard_worker.py <rank> <world> <port> <out.npz> <save_dir> <timing>
 
 All ranks share ONE GPU (the test boxes have one), so the process group is "gloo" and dist.py stages its collectives through
-host memory; the kernels and the host logic of RetrievalTrainer._validate_epoch_sharded are exactly those of an RCCL run.
+host memory; the kernels and the host logic of validation.validate_epoch are exactly those of an RCCL run.
 Every rank builds the same loader (seeded), validates it sharded and writes the flattened dictionary.  timing = 1: the wall time
 of the replicated and of the sharded validation of a larger loader as well (several processes on one device: overhead only).
 The parent imports loader(), trainer(), validate() and flatten() for its single-process run of the same thing.
