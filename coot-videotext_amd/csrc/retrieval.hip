@@ -398,6 +398,222 @@ TkWs tk_layout(void* base, int M, int N, int K, int S) {
   return w;
 }
 
+// ---- labelled ranking: M queries, N gallery rows, labels[i] = the gallery row of query i (coot_retrieval_ranks_labeled) ------
+// The ranks of coot_retrieval_ranks without the diagonal assumption: several queries per gallery row, gallery rows without a
+// query, queries without a row (a label outside [0, N): rank -1, in neither direction's metrics, never used as an index).
+//   query -> gallery: ranks_q[i] = #{j != g : (s_ij, j) ahead of (s_ig, g)}, g = labels[i]
+//   gallery -> query: the best positive of column j is the valid query i with labels[i] = j that is ahead of the others,
+//                     (t_j, a_j) = (s_ij, i);  ranks_g[j] = #{i' : (s_i'j, i') ahead of (t_j, a_j)}: the best-ranked ground truth
+// "ahead" = the tie rule above (larger, or equal with a later index).  s is the tile_dot chain, never stored:
+//   rt_lab_own_kernel: own[i] = s[i, labels[i]] by the chain of tile_dot (64 queries per workgroup, the operands staged as there,
+//     gallery rows gathered; one thread per query walks k, zero padding of the last chunk included: the accumulators' bits), and
+//     an integer atomic max of the (score, i) word into best[j]: independent of the schedule.  best = 0: no valid query.
+//   rt_lab_prepare_kernel: ranks_q / ranks_g = 0 or -1, n_valid.
+//   rt_lab_rank_kernel: rt_rank_kernel's counting with thresholds (own[i], labels[i]) per row and (t_j, a_j) per column.
+//   rt_lab_metrics_kernel: rt_metrics_kernel over the entries >= 0 of each vector.
+template <bool NORM>
+__global__ __launch_bounds__(256) void rt_lab_own_kernel(const float* A, const float* B, const int* labels, const float* nA, const float* nB, int M,
+                                                         int N, int d, float* own, tk_entry_t* best) {
+  __shared__ float As[RT][RP], Bs[RT][RP];
+  __shared__ int lab[RT];
+  const int tid = threadIdx.x, i0 = blockIdx.x * RT;
+  if (tid < RT) {
+    const int g = i0 + tid < M ? labels[i0 + tid] : -1;
+    lab[tid] = (unsigned)g < (unsigned)N ? g : -1;  // -1: no ground truth (or no such query): staged as zeros, nothing written
+  }
+  __syncthreads();
+  int gq[8];  // the gallery rows of the 8 queries this thread stages (the same rows in every chunk)
+  float ra[8], rb[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const int r = (tid >> 5) + 8 * q;
+    gq[q] = lab[r];
+    ra[q] = NORM && gq[q] >= 0 ? nA[i0 + r] : 1.f;
+    rb[q] = NORM && gq[q] >= 0 ? nB[gq[q]] : 1.f;
+  }
+  float acc = 0.f;
+  for (int k0 = 0; k0 < d; k0 += RK) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int e = tid + 256 * q, r = e >> 5, k = e & 31;
+      const bool in = k0 + k < d && gq[q] >= 0;
+      if (NORM) {
+        As[r][k] = in ? A[(long)(i0 + r) * d + k0 + k] / ra[q] : 0.f;
+        Bs[r][k] = in ? B[(long)gq[q] * d + k0 + k] / rb[q] : 0.f;
+      } else {
+        As[r][k] = in ? A[(long)(i0 + r) * d + k0 + k] : 0.f;
+        Bs[r][k] = in ? B[(long)gq[q] * d + k0 + k] : 0.f;
+      }
+    }
+    __syncthreads();
+    if (tid < RT) {
+#pragma unroll 8
+      for (int k = 0; k < RK; ++k) acc = fmaf(As[tid][k], Bs[tid][k], acc);
+    }
+    __syncthreads();
+  }
+  if (tid < RT && lab[tid] >= 0) {
+    own[i0 + tid] = acc;
+    atomicMax(best + lab[tid], tk_pack(acc, i0 + tid));
+  }
+}
+
+// one workgroup: the rank vectors start at 0 where there is a ground truth and stay -1 elsewhere; n_valid = the numbers of both
+__global__ __launch_bounds__(1024) void rt_lab_prepare_kernel(const int* labels, const tk_entry_t* best, int M, int N, int* ranks_q, int* ranks_g,
+                                                              int* n_valid) {
+  __shared__ int s_n[2];
+  const int tid = threadIdx.x;
+  if (tid < 2) s_n[tid] = 0;
+  __syncthreads();
+  int nq = 0, ng = 0;
+  for (int i = tid; i < M; i += 1024) {
+    const bool v = (unsigned)labels[i] < (unsigned)N;
+    ranks_q[i] = v ? 0 : -1; nq += v;
+  }
+  for (int j = tid; j < N; j += 1024) {
+    const bool v = best[j] != 0ull;
+    ranks_g[j] = v ? 0 : -1; ng += v;
+  }
+  if (nq) atomicAdd(&s_n[0], nq);
+  if (ng) atomicAdd(&s_n[1], ng);
+  __syncthreads();
+  if (tid < 2) n_valid[tid] = s_n[tid];
+}
+
+// every tile of s: grid (column tiles, row tiles); row counts -> ranks_q, column counts -> ranks_g
+// (waves_per_eu: NORM would take 130 VGPRs, two more than 4 waves per SIMD allow — rt_rank_kernel's occupancy; no spill at 128)
+template <bool NORM>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void rt_lab_rank_kernel(const float* A, const float* B, const int* labels, const float* nA, const float* nB, int M,
+                                                          int N, int d, const float* own, const tk_entry_t* best, float* sim, int* ranks_q,
+                                                          int* ranks_g) {
+  __shared__ float As[RT][RP], Bs[RT][RP];
+  __shared__ int rowc[RT], colc[RT];
+  const int i0 = blockIdx.y * RT, j0 = blockIdx.x * RT;
+  const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
+  if (tid < RT) { rowc[tid] = 0; colc[tid] = 0; }
+  Tile t;
+  tile_dot<NORM>(A, B, M, N, d, i0, j0, As, Bs, t, nA, nB);  // ends with a barrier: the counters are zeroed
+  float di[4], tj[4];
+  int gi[4], aj[4];  // gi: the row's label, -1 = none;  aj: the column's best positive query, -1 = none
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int i = i0 + 4 * ty + r, g = i < M ? labels[i] : -1;
+    gi[r] = (unsigned)g < (unsigned)N ? g : -1;
+    di[r] = gi[r] >= 0 ? own[i] : 0.f;
+  }
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const int j = j0 + 4 * tx + c;
+    const tk_entry_t e = j < N ? best[j] : 0ull;
+    aj[c] = e ? (int)(unsigned)e : -1;
+    tj[c] = tk_score(e);
+  }
+  int rc[4] = {0, 0, 0, 0}, cc[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int i = i0 + 4 * ty + r, j = j0 + 4 * tx + c;
+      if (i < M && j < N) {
+        const float s = t.acc[r][c];
+        if (sim) sim[(long)i * N + j] = s;
+        // row i: is j ahead of the label's column?   column j: is i ahead of the column's best positive?
+        if (gi[r] >= 0 && j != gi[r] && (s > di[r] || (s == di[r] && j > gi[r]))) ++rc[r];
+        if (aj[c] >= 0 && (s > tj[c] || (s == tj[c] && i > aj[c]))) ++cc[c];
+      }
+    }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) if (rc[r]) atomicAdd(&rowc[4 * ty + r], rc[r]);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) if (cc[c]) atomicAdd(&colc[4 * tx + c], cc[c]);
+  __syncthreads();
+  if (tid < RT) {
+    if (i0 + tid < M && rowc[tid]) atomicAdd(ranks_q + i0 + tid, rowc[tid]);
+    if (j0 + tid < N && colc[tid]) atomicAdd(ranks_g + j0 + tid, colc[tid]);
+  }
+}
+
+// rt_metrics_kernel over the n entries >= 0 of each vector: workgroup 0 = ranks_q [M], ranks in [0, N), hist [N];
+// workgroup 1 = ranks_g [N], ranks in [0, M), hist + N [M].  hist zeroed.  n = 0: seven zeros.
+__global__ __launch_bounds__(1024) void rt_lab_metrics_kernel(const int* ranks_q, const int* ranks_g, int M, int N, int* hist, float* out) {
+  __shared__ unsigned long long s_sum;
+  __shared__ int s_cnt[5];  // < 1, < 5, < 10, < 50, n
+  __shared__ int s_scan[1024];
+  __shared__ int s_med[2];
+  const int* ranks = blockIdx.x == 0 ? ranks_q : ranks_g;
+  const int len = blockIdx.x == 0 ? M : N, H = blockIdx.x == 0 ? N : M;
+  int* h = blockIdx.x == 0 ? hist : hist + N;
+  const int tid = threadIdx.x;
+  if (tid == 0) { s_sum = 0ull; s_med[0] = -1; s_med[1] = -1; }
+  if (tid < 5) s_cnt[tid] = 0;
+  __syncthreads();
+  unsigned long long ls = 0ull;
+  int lc[5] = {0, 0, 0, 0, 0};
+  for (int i = tid; i < len; i += 1024) {
+    const int r = ranks[i];
+    if (r < 0) continue;
+    ls += (unsigned long long)r;
+    lc[0] += r < 1; lc[1] += r < 5; lc[2] += r < 10; lc[3] += r < 50; ++lc[4];
+    if (r < H) atomicAdd(h + r, 1);  // (a rank is < H: never outside hist)
+  }
+  atomicAdd(&s_sum, ls);
+#pragma unroll
+  for (int q = 0; q < 5; ++q) if (lc[q]) atomicAdd(&s_cnt[q], lc[q]);
+  __threadfence();
+  __syncthreads();
+  const int n = s_cnt[4];
+  // order statistics (n - 1) / 2 and n / 2 (0-based) of the sorted ranks: np.median averages them
+  const int per = (H + 1023) / 1024, lo = min(H, tid * per), hi = min(H, lo + per);
+  int part = 0;
+  for (int v = lo; v < hi; ++v) part += __hip_atomic_load(h + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // the counts were made with device atomics
+  s_scan[tid] = part;
+  __syncthreads();
+  if (tid == 0) {
+    int run = 0;
+    for (int q = 0; q < 1024; ++q) { const int c = s_scan[q]; s_scan[q] = run; run += c; }
+  }
+  __syncthreads();
+  const int k0 = (n - 1) / 2, k1 = n / 2;
+  int run = s_scan[tid];
+  for (int v = lo; v < hi; ++v) {
+    const int c = __hip_atomic_load(h + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (c) {
+      if (k0 >= run && k0 < run + c) s_med[0] = v;
+      if (k1 >= run && k1 < run + c) s_med[1] = v;
+      run += c;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float* o = out + 7 * blockIdx.x;
+    if (n == 0) {
+      for (int q = 0; q < 7; ++q) o[q] = 0.f;
+    } else {
+      const float nf = (float)n;
+      const float r1 = s_cnt[0] / nf, r5 = s_cnt[1] / nf, r10 = s_cnt[2] / nf, r50 = s_cnt[3] / nf;
+      const double med = 0.5 * ((double)s_med[0] + (double)s_med[1]);
+      o[0] = r1; o[1] = r5; o[2] = r10; o[3] = r50;
+      o[4] = (float)(floor(med) + 1.0);
+      o[5] = (float)((double)s_sum / (double)n + 1.0);
+      o[6] = r1 + r5 + r50;
+    }
+  }
+}
+
+// best and hist are adjacent: one zero fill
+struct LabWs { float *na, *nb, *own; tk_entry_t* best; int* hist; size_t zero_bytes, bytes; };
+LabWs lab_layout(void* base, int M, int N) {
+  LabWs w; size_t off = 0;
+  auto take = [&](size_t n) { char* p = base ? (char*)base + off : nullptr; off += (n + 255) & ~(size_t)255; return (void*)p; };
+  w.na = (float*)take((size_t)M * 4); w.nb = (float*)take((size_t)N * 4); w.own = (float*)take((size_t)M * 4);
+  const size_t z0 = off;
+  w.best = (tk_entry_t*)take((size_t)N * 8);
+  w.hist = (int*)take(((size_t)N + M) * 4);
+  w.zero_bytes = off - z0;
+  w.bytes = off;
+  return w;
+}
+
 }  // namespace
 void set_rt_topk_splits(int n) { g_rt_topk_splits = n; }
 int get_rt_topk_splits() { return g_rt_topk_splits; }
@@ -500,6 +716,52 @@ int coot_retrieval_topk(const float* queries, const float* gallery, int M, int N
   if (sp.S > 1) {
     hipLaunchKernelGGL(rt_topk_merge_kernel, dim3((M + 3) / 4), dim3(256), 0, st, (const tk_entry_t*)w.part, M, sp.S, K, (int*)idx_out, score_out);
     COOT_CHECK_LAUNCH("rt_topk_merge");
+  }
+  return 0;
+}
+
+size_t coot_retrieval_ranks_labeled_workspace_bytes(int M, int N, int d) {
+  (void)d;  // no normalised copy is kept: the norms only
+  if (M < 1 || N < 1) return 0;
+  return lab_layout(nullptr, M, N).bytes;  // exact: the call refuses one byte less
+}
+
+int coot_retrieval_ranks_labeled(const float* queries, const float* gallery, const int32_t* labels, int M, int N, int d, int normalize,
+                                 int32_t* ranks_q, int32_t* ranks_g, int32_t* n_valid, float* metrics, float* sim_out, void* workspace,
+                                 size_t workspace_bytes, coot_stream_t stream) {
+  COOT_REQUIRE(queries && gallery && labels && ranks_q && ranks_g && n_valid && workspace, "retrieval_labeled: null pointer");
+  COOT_REQUIRE(M >= 1 && N >= 1 && d >= 1 && (M + RT - 1) / RT <= 65535, "retrieval_labeled: M = %d, N = %d, d = %d", M, N, d);
+  COOT_REQUIRE(((uintptr_t)workspace & 7) == 0, "retrieval_labeled: workspace is not 8-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  LabWs w = lab_layout(workspace, M, N);
+  COOT_REQUIRE(w.bytes <= workspace_bytes, "retrieval_labeled: workspace too small (%zu < %zu)", workspace_bytes, w.bytes);
+  const int mt = (M + RT - 1) / RT, nt = (N + RT - 1) / RT;
+  const int* lab = (const int*)labels;
+  if (int rc = check_hip(hipMemsetAsync(w.best, 0, w.zero_bytes, st), "memset best, hist")) return rc;
+  if (normalize) {
+    hipLaunchKernelGGL(rt_norms_kernel, dim3((M + N + 3) / 4), dim3(256), 0, st, queries, M, gallery, N, d, w.na, w.nb);
+    COOT_CHECK_LAUNCH("rt_norms");
+    hipLaunchKernelGGL(rt_lab_own_kernel<true>, dim3(mt), dim3(256), 0, st, queries, gallery, lab, (const float*)w.na, (const float*)w.nb, M, N, d,
+                       w.own, w.best);
+  } else {
+    hipLaunchKernelGGL(rt_lab_own_kernel<false>, dim3(mt), dim3(256), 0, st, queries, gallery, lab, (const float*)nullptr, (const float*)nullptr, M, N,
+                       d, w.own, w.best);
+  }
+  COOT_CHECK_LAUNCH("rt_lab_own");
+  hipLaunchKernelGGL(rt_lab_prepare_kernel, dim3(1), dim3(1024), 0, st, lab, (const tk_entry_t*)w.best, M, N, (int*)ranks_q, (int*)ranks_g,
+                     (int*)n_valid);
+  COOT_CHECK_LAUNCH("rt_lab_prepare");
+  if (normalize) {
+    hipLaunchKernelGGL(rt_lab_rank_kernel<true>, dim3(nt, mt), dim3(256), 0, st, queries, gallery, lab, (const float*)w.na, (const float*)w.nb, M, N, d,
+                       (const float*)w.own, (const tk_entry_t*)w.best, sim_out, (int*)ranks_q, (int*)ranks_g);
+  } else {
+    hipLaunchKernelGGL(rt_lab_rank_kernel<false>, dim3(nt, mt), dim3(256), 0, st, queries, gallery, lab, (const float*)nullptr, (const float*)nullptr, M,
+                       N, d, (const float*)w.own, (const tk_entry_t*)w.best, sim_out, (int*)ranks_q, (int*)ranks_g);
+  }
+  COOT_CHECK_LAUNCH("rt_lab_rank");
+  if (metrics) {
+    hipLaunchKernelGGL(rt_lab_metrics_kernel, dim3(2), dim3(1024), 0, st, (const int*)ranks_q, (const int*)ranks_g, M, N, w.hist, metrics);
+    COOT_CHECK_LAUNCH("rt_lab_metrics");
   }
   return 0;
 }

@@ -12,7 +12,11 @@ device (similarities and selection fused, no M x N matrix).
 
 Sharded validation (data-parallel runs): retrieval_ranks_part_device counts one strip of rows, an integer all-reduce of the
 strips is the whole (compute_retrieval_device(dp=...)), retrieval_metrics_device turns rank vectors into the metrics;
-compute_retrieval_counts_part is the host mirror of a strip."""
+compute_retrieval_counts_part is the host mirror of a strip.
+
+Labelled ranking (compute_retrieval_labeled / retrieval_ranks_labeled_device / compute_retrieval_labeled_device): the ranks and
+metrics without the assumption "square, ground truth on the diagonal" — M queries, N gallery rows, labels[i] = the gallery row of
+query i; several queries per row, rows without a query and queries without a row (a label outside [0, N)) are allowed."""
 from __future__ import annotations
 
 import ctypes as C
@@ -98,6 +102,95 @@ def retrieval_topk_device(queries, gallery, k: int, normalize: bool = False, wan
                                        sim.data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(),
                                        torch.cuda.current_stream().cuda_stream), "coot_retrieval_topk")
     return idx, scores, sim
+
+
+def _ahead(s, idx, t, a):
+    """The device tie rule: entry (s, idx) is ahead of (t, a) when it is larger, or equal with a later index."""
+    return (s > t) | ((s == t) & (idx > a))
+
+
+def _labeled_metrics(ranks: np.ndarray) -> Tuple[Dict[str, float], np.ndarray]:
+    """The seven metrics over the entries >= 0 of a rank vector, in the fp32 / fp64 steps of the device kernel, as a dictionary
+    and as the float32 [7] the device writes (n == 0: zeros)."""
+    r = ranks[ranks >= 0].astype(np.int64)
+    n = len(r)
+    out = np.zeros(7, np.float32)
+    if n:
+        nf = np.float32(n)
+        r1, r5, r10, r50 = [np.float32((r < k).sum()) / nf for k in (1, 5, 10, 50)]
+        r = np.sort(r)
+        med = 0.5 * (np.float64(r[(n - 1) // 2]) + np.float64(r[n // 2]))
+        out[:] = [r1, r5, r10, r50, np.float32(np.floor(med) + 1.0), np.float32(np.float64(r.sum()) / np.float64(n) + 1.0), (r1 + r5) + r50]
+    return {k: float(v) for k, v in zip(VALKEYS, out)}, out
+
+
+def compute_retrieval_labeled(sim: np.ndarray, labels: np.ndarray):
+    """Host mirror of coot_retrieval_ranks_labeled on a similarity matrix sim [M, N] (queries x gallery): labels[i] is the gallery
+    row of query i; a label outside [0, N) means "no ground truth" (rank -1, in neither direction's ranks or metrics).  Returns
+    (res_q2g, res_g2q, ranks_q int32 [M], ranks_g int32 [N]).
+    ranks_q[i] = the entries (s[i, j], j), j != g, ahead of (s[i, g], g), g = labels[i]: the position of g in
+    np.argsort(sim[i], kind="stable")[::-1].  ranks_g[j] = the entries (s[i', j], i') of column j ahead of the column's best
+    positive, the query with labels[i] == j that is ahead of the other ones: the minimum over the column's ground-truth queries of
+    their position in np.argsort(sim[:, j], kind="stable")[::-1]; -1 for gallery rows without a valid query.  The metric
+    dictionaries (VALKEYS) are taken over the valid entries of each direction (n == 0: zeros)."""
+    sim = np.asarray(sim)
+    labels = np.asarray(labels).astype(np.int64).reshape(-1)
+    m, n = sim.shape
+    assert labels.shape == (m,), (sim.shape, labels.shape)
+    valid = (labels >= 0) & (labels < n)
+    ranks_q, ranks_g = np.full(m, -1, np.int32), np.full(n, -1, np.int32)
+    cols = np.arange(n)
+    for i in np.nonzero(valid)[0]:
+        g = labels[i]
+        ranks_q[i] = ((cols != g) & _ahead(sim[i], cols, sim[i, g], g)).sum()
+    rows = np.arange(m)
+    for j in np.unique(labels[valid]):
+        col = sim[:, j]
+        t, a = None, -1
+        for i in np.nonzero(valid & (labels == j))[0]:  # ascending i: an equal score with a later index is ahead
+            if t is None or col[i] >= t:
+                t, a = col[i], i
+        ranks_g[j] = _ahead(col, rows, t, a).sum()
+    res_q, _ = _labeled_metrics(ranks_q)
+    res_g, _ = _labeled_metrics(ranks_g)
+    return res_q, res_g, ranks_q, ranks_g
+
+
+def retrieval_ranks_labeled_device(queries, gallery, labels, normalize: bool = False, want_sim: bool = False):
+    """queries [M, d], gallery [N, d]: cuda float32; labels: cuda int32 [M].  Returns (ranks_q int32 [M], ranks_g int32 [N],
+    n_valid int32 [2], metrics float32 [2, 7], sim [M, N] or None), all on the device (no synchronisation): compute_retrieval_labeled
+    of the fp32 similarities retrieval_topk_device selects from, without the M x N matrix (want_sim is a testing aid)."""
+    import torch
+    from . import lib as _lib
+    queries, gallery = _device_pair("retrieval_ranks_labeled_device", "compute_retrieval_labeled", queries, gallery, torch.float32, same_shape=False)
+    if not labels.is_cuda:
+        raise RuntimeError("retrieval_ranks_labeled_device needs CUDA tensors (there is no CPU fallback; use compute_retrieval_labeled)")
+    (m, d), n = queries.shape, gallery.shape[0]
+    assert labels.dtype == torch.int32 and labels.shape == (m,), (labels.dtype, labels.shape, m)
+    labels = labels.contiguous()
+    lib = _lib.load()
+    dev = queries.device
+    ws = torch.empty(lib.coot_retrieval_ranks_labeled_workspace_bytes(m, n, d), dtype=torch.uint8, device=dev)
+    ranks_q = torch.empty(m, dtype=torch.int32, device=dev)
+    ranks_g = torch.empty(n, dtype=torch.int32, device=dev)
+    n_valid = torch.empty(2, dtype=torch.int32, device=dev)
+    met = torch.empty(2, 7, dtype=torch.float32, device=dev)
+    sim = torch.empty(m, n, dtype=torch.float32, device=dev) if want_sim else None
+    _lib.check(lib.coot_retrieval_ranks_labeled(queries.data_ptr(), gallery.data_ptr(), labels.data_ptr(), m, n, d, int(normalize),
+                                                ranks_q.data_ptr(), ranks_g.data_ptr(), n_valid.data_ptr(), met.data_ptr(),
+                                                sim.data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(),
+                                                torch.cuda.current_stream().cuda_stream), "coot_retrieval_ranks_labeled")
+    return ranks_q, ranks_g, n_valid, met, sim
+
+
+def compute_retrieval_labeled_device(queries, gallery, labels, normalize: bool = False):
+    """Device version of compute_retrieval_labeled for embeddings (not a similarity matrix): (res_q2g, res_g2q, sum_at_1) with the
+    reference's dictionary keys, as compute_retrieval_device returns them.  One 56-byte D2H copy."""
+    met = retrieval_ranks_labeled_device(queries, gallery, labels, normalize)[3]
+    m = met.cpu().numpy().astype(np.float64)
+    res1 = {k: float(v) for k, v in zip(VALKEYS, m[0])}
+    res2 = {k: float(v) for k, v in zip(VALKEYS, m[1])}
+    return res1, res2, (res1["r1"] + res2["r1"]) / 2
 
 
 def strip_bounds(n: int, world: int, rank: int) -> Tuple[int, int]:

@@ -358,6 +358,35 @@ size_t coot_retrieval_topk_workspace_bytes(int M, int N, int d, int K);
 int coot_retrieval_topk(const float* queries, const float* gallery, int M, int N, int d, int K, int normalize, int32_t* idx_out,
                         float* score_out, float* sim_out, void* workspace, size_t workspace_bytes, coot_stream_t stream);
 
+/* ---- labelled retrieval ranking on the device: M queries, N gallery rows, several queries per row -----------------------
+ * coot_retrieval_ranks without the assumption "N x N, ground truth on the diagonal": labels[i] (device int32 [M]) is the gallery
+ * row of query i.  Several queries may share a row (a second annotation set, several captions per clip), rows may have no query
+ * (distractors), and a label outside [0, N), e.g. -1, means "no ground truth": it is never used as an index, the query's rank is -1
+ * and it enters neither direction's ranks nor metrics (as a competitor in its columns it still counts).
+ *   normalize != 0: every row of both sets is divided by sqrt(sum x^2), no eps, at staging (no normalised copy, as in
+ *   coot_retrieval_topk);  s = queries . gallery^T is the fp32 FMA chain of coot_retrieval_ranks and coot_retrieval_topk (k order,
+ *   chunks of 32): the optional sim_out [M, N] (testing aid) equals coot_retrieval_topk's bit for bit;
+ *   "ahead": (score, index) is ahead of (t, a) when score > t, or score == t and index > a (float comparison: -0 == +0);
+ *   ranks_q[i] = #{j != g : (s[i,j], j) ahead of (s[i,g], g)}, g = labels[i] = the position of g in
+ *   np.argsort(s[i], kind="stable")[::-1];
+ *   ranks_g[j], for a gallery row j that is the label of at least one valid query: let (t, a) = (s[i,j], i) of the query i with
+ *   labels[i] == j that is ahead of all others (the best positive); ranks_g[j] = #{i' in [0, M) : (s[i',j], i') ahead of (t, a)} =
+ *   the minimum over those queries of their position in np.argsort(s[:, j], kind="stable")[::-1] (the multi-caption protocol:
+ *   the best-ranked ground truth counts).  Rows without a valid query: ranks_g[j] = -1;
+ *   n_valid [2] = (n_q, n_g): the valid queries and the gallery rows that have one;
+ *   metrics (optional, [2, 7]): {r1, r5, r10, r50, medr, meanr, sum} query -> gallery, then gallery -> query, each over its n
+ *   entries >= 0 with the arithmetic of coot_retrieval_ranks (r@k = float(count) / float(n), medr = floor(median) + 1 in double,
+ *   meanr = float(double(sum) / n + 1), sum = r1 + r5 + r50 in fp32); n == 0: seven zeros.
+ * For M == N and labels[i] == i: ranks_q, ranks_g and metrics are coot_retrieval_ranks' ranks_12, ranks_21 and metrics bit for bit.
+ * A row or column with a non-finite similarity has unspecified ranks.  M, N, d >= 1.  No M x N array exists unless sim_out is
+ * given; every result is an integer function of s (integer atomics only), so it does not depend on the workgroup schedule.
+ * workspace (8-byte aligned): coot_retrieval_ranks_labeled_workspace_bytes(M, N, d), exact = (2 M + N) floats, N 64-bit words and
+ * (M + N) int32, each rounded up to 256 bytes.  The call retains no pointer and does not synchronise. */
+size_t coot_retrieval_ranks_labeled_workspace_bytes(int M, int N, int d);
+int coot_retrieval_ranks_labeled(const float* queries, const float* gallery, const int32_t* labels, int M, int N, int d, int normalize,
+                                 int32_t* ranks_q, int32_t* ranks_g, int32_t* n_valid, float* metrics, float* sim_out, void* workspace,
+                                 size_t workspace_bytes, coot_stream_t stream);
+
 /* ---- the whole training step as native code (coot/trainer_retrieval.py:253-291) -------------------------------
  * Networks are indexed 0 = net_video_local, 1 = net_video_global, 2 = net_text_local, 3 = net_text_global
  * (coot/configs_retrieval.py:182-189).  All buffers are caller-owned device memory. */
