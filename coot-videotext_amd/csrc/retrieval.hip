@@ -273,6 +273,34 @@ __device__ __forceinline__ int tk_ahead(const tk_entry_t* L, int n, tk_entry_t v
   return lo;
 }
 
+// One wave folds nc <= 64 candidates C into the sorted list L of n entries, of which the K best stay: the new position of an entry
+// is the number of entries ahead of it.  read() takes every entry and counts; place() writes them after a barrier of the waves
+// that share the list (every entry is read before one is placed).
+struct TkFold {
+  tk_entry_t ec, e0, e1;
+  int pc, p0, p1;
+  bool hc, h0, h1;
+  __device__ __forceinline__ void read(const tk_entry_t* L, int n, const tk_entry_t* C, int nc, int lane) {
+    hc = lane < nc; h0 = lane < n; h1 = lane + 64 < n;
+    ec = 0ull; e0 = 0ull; e1 = 0ull;
+    pc = 0; p0 = lane; p1 = lane + 64;
+    if (nc) {
+      if (hc) { ec = C[lane]; pc = tk_ahead(L, n, ec); }
+      if (h0) e0 = L[lane];
+      if (h1) e1 = L[lane + 64];
+      for (int q = 0; q < nc; ++q) {
+        const tk_entry_t v = C[q];
+        pc += v > ec; p0 += v > e0; p1 += v > e1;
+      }
+    }
+  }
+  __device__ __forceinline__ void place(tk_entry_t* L, int K) const {
+    if (hc && pc < K) L[pc] = ec;
+    if (h0 && p0 < K) L[p0] = e0;
+    if (h1 && p1 < K) L[p1] = e1;
+  }
+};
+
 size_t tk_lds_bytes(int K) { return (size_t)2 * RT * RP * 4 + (size_t)RT * RT * 8 + (size_t)RT * K * 8 + 2 * RT * 4; }
 
 // grid (S, row tiles); LDS: As | Bs | cand [RT][RT] | list [RT][K] | cnt [RT] | ncand [RT]   (tk_lds_bytes)
@@ -318,23 +346,11 @@ __global__ __launch_bounds__(256) void rt_topk_kernel(const float* A, const floa
       const int nc = ncand[row], n = cnt[row];
       tk_entry_t* L = list + row * K;
       const tk_entry_t* C = cand + row * RT;
-      const bool hc = lane < nc, h0 = lane < n, h1 = lane + 64 < n;
-      tk_entry_t ec = 0ull, e0 = 0ull, e1 = 0ull;
-      int pc = 0, p0 = lane, p1 = lane + 64;
-      if (nc) {
-        if (hc) { ec = C[lane]; pc = tk_ahead(L, n, ec); }
-        if (h0) e0 = L[lane];
-        if (h1) e1 = L[lane + 64];
-        for (int q = 0; q < nc; ++q) {
-          const tk_entry_t v = C[q];
-          pc += v > ec; p0 += v > e0; p1 += v > e1;
-        }
-      }
+      TkFold f;
+      f.read(L, n, C, nc, lane);
       __syncthreads();
       if (nc) {
-        if (hc && pc < K) L[pc] = ec;
-        if (h0 && p0 < K) L[p0] = e0;
-        if (h1 && p1 < K) L[p1] = e1;
+        f.place(L, K);
         if (lane == 0) { cnt[row] = min(K, n + nc); ncand[row] = 0; }
       }
     }
@@ -396,6 +412,239 @@ TkWs tk_layout(void* base, int M, int N, int K, int S) {
   w.part = (tk_entry_t*)take(S > 1 ? (size_t)M * S * K * 8 : 0);
   w.bytes = off;
   return w;
+}
+
+// ---- top-K for a few queries on a prepared gallery (coot_retrieval_topk_few) ---------------------------------------------------
+// The search as it is used after training: M <= 16 queries against a gallery that stays in HBM, its row norms computed once
+// (coot_retrieval_row_norms).  One sweep of the gallery bounds the call, so the 64 x 64 tile (at most 64 workgroups for one row
+// tile, 63 of 64 accumulator rows padding at M = 1) is replaced by one gallery row per thread and one accumulator per query;
+// element (i, j) is still tile_dot's chain — acc = fmaf(q_ik, g_jk, acc) from +0 over k in order, the zero padding of the last
+// chunk of 32 included, operands divided by their row norms at staging — so sim, idx and scores are coot_retrieval_topk's bits.
+//   rt_few_prep_kernel: the operand table qn [dpad][16] = q_ik / |q_i| (zeros beyond M and d), the same for every gallery row.
+//   rt_few_kernel: workgroup s (128 threads) sweeps a contiguous range of 128-row blocks.  Per chunk of 32 k: the block's
+//     128 x 32 floats (coalesced 16-byte loads, divided by the row norm) and the table's 32 x 16 go to LDS, then a thread walks
+//     its own row (stride RP: no bank conflict) against broadcast reads of the queries.  The next chunk's global loads are issued
+//     before the FMAs and several workgroups share a CU: the loads in flight hide the HBM latency.  Selection as in
+//     rt_topk_kernel: a sorted list of <= K entries per query, candidates that beat the K-th entry, folded in by rank (TkFold);
+//     the candidate buffer lies over the tile, which is idle then.
+//   rt_few_merge_kernel: rt_topk_merge_kernel's merge by rank over <= 32 lists held in LDS, one workgroup of 1 024 threads per (group, query); a
+//     round writes entry lists again (782 lists -> 25 -> the result), the last one idx / score.  Unfilled slots (0) rank behind
+//     every entry and land on the unfilled slots of the merged list, so short lists (K > rows of a workgroup) pass through.
+constexpr int FEW_MAX = COOT_RETRIEVAL_FEW_MAX;  // queries
+constexpr int FR = 128;                          // gallery rows per step = threads per workgroup
+constexpr int FEW_SMAX = 1024;                   // row splits: about four workgroups per CU
+constexpr int FEW_G = 32;                        // lists per merge workgroup
+constexpr int FEW_MT = 1024;                     // threads of a merge workgroup: the searches are LDS latency, so as many waves as fit
+int g_rt_few_splits = 0;                         // coot_set_option("rt_few_splits", n) (tests); 0 = automatic
+static_assert(FEW_MAX * FR * 8 <= (FR * RP + RK * FEW_MAX) * 4, "the candidate buffer lies over the staged tile");
+
+// one wave per query slot: the norm of rt_norms_kernel, column i of the table (slots beyond M: zeros)
+__global__ __launch_bounds__(64) void rt_few_prep_kernel(const float* q, int M, int d, int dpad, int norm, float* qnorm, float* qn) {
+  const int i = blockIdx.x, lane = threadIdx.x;
+  if (i >= M) {
+    for (int k = lane; k < dpad; k += 64) qn[k * FEW_MAX + i] = 0.f;
+    return;
+  }
+  const float* src = q + (long)i * d;
+  const float nrm = norm ? sqrtf(row_sumsq(src, d, lane)) : 1.f;
+  if (lane == 0) qnorm[i] = nrm;
+  for (int k = lane; k < dpad; k += 64) qn[k * FEW_MAX + i] = k < d ? (norm ? src[k] / nrm : src[k]) : 0.f;
+}
+
+size_t few_lds_bytes(int MQ, int K) { return (size_t)(FR * RP + RK * FEW_MAX) * 4 + (size_t)MQ * K * 8 + 2 * FEW_MAX * 4; }
+
+// grid (S); MQ = M rounded up to 1, 2, 4, 8, 16 accumulators; LDS: tile [FR][RP] | qs [RK][16] | list [MQ][K] | cnt | ncand
+template <int MQ, bool NORM>
+__global__ __launch_bounds__(FR) void rt_few_kernel(const float* __restrict__ G, const float* __restrict__ gnorm, const float* __restrict__ qn, int M,
+                                                    int N, int d, int K, int blocks_per_split, int S, int vec, float* __restrict__ sim,
+                                                    tk_entry_t* __restrict__ part, int* __restrict__ idx_out, float* __restrict__ score_out) {
+  extern __shared__ __attribute__((aligned(16))) char few_lds[];
+  float* tile = (float*)few_lds;
+  float* qs = tile + FR * RP;
+  tk_entry_t* cand = (tk_entry_t*)few_lds;  // [MQ][FR], between the last FMA of a block and the next block's staging
+  tk_entry_t* list = (tk_entry_t*)(qs + RK * FEW_MAX);
+  int* cnt = (int*)(list + MQ * K);
+  int* ncand = cnt + FEW_MAX;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int nb = (N + FR - 1) / FR, nchunks = (d + RK - 1) / RK;
+  const int b0 = blockIdx.x * blocks_per_split, b1 = min(nb, b0 + blocks_per_split);
+  const int sr = tid >> 3, sk = (tid & 7) * 4;  // staging: floats sk .. sk + 3 of the rows sr + 16 q of a chunk
+  if (tid < FEW_MAX) { cnt[tid] = 0; ncand[tid] = 0; }
+  for (int e = tid; e < MQ * K; e += FR) list[e] = 0ull;  // 0 = behind every entry: an unfilled slot
+  for (int b = b0; b < b1; ++b) {
+    const int j0 = b * FR;
+    float rb[8];
+    if (NORM) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) rb[q] = j0 + sr + 16 * q < N ? gnorm[j0 + sr + 16 * q] : 1.f;
+    }
+    float4 pf[8], pq;
+    // one chunk into registers: 8 x 16 bytes of the gallery and 16 of the table per thread.  No branch: an address beyond N or d
+    // is clamped into the gallery and its value is dropped at staging
+    auto load = [&](int k0) {
+      const int k = k0 + sk;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const float* p = G + (long)min(j0 + sr + 16 * q, N - 1) * d;
+        if (vec) {
+          pf[q] = *(const float4*)(p + (k < d ? k : 0));
+        } else {
+          pf[q].x = p[min(k, d - 1)]; pf[q].y = p[min(k + 1, d - 1)]; pf[q].z = p[min(k + 2, d - 1)]; pf[q].w = p[min(k + 3, d - 1)];
+        }
+      }
+      pq = *(const float4*)(qn + (long)k0 * FEW_MAX + tid * 4);
+    };
+    float acc[MQ];
+#pragma unroll
+    for (int i = 0; i < MQ; ++i) acc[i] = 0.f;
+    load(0);
+    for (int c = 0; c < nchunks; ++c) {
+      const int k0 = c * RK;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int r = sr + 16 * q;
+        const bool rin = j0 + r < N;
+        const float v[4] = {pf[q].x, pf[q].y, pf[q].z, pf[q].w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e)  // rows beyond N and columns beyond d are zero, as tile_dot stages them
+          tile[r * RP + sk + e] = (rin && k0 + sk + e < d) ? (NORM ? v[e] / rb[q] : v[e]) : 0.f;
+      }
+      *(float4*)(qs + tid * 4) = pq;
+      __syncthreads();
+      if (c + 1 < nchunks) load(k0 + RK);  // in flight under the FMAs
+#pragma unroll 4
+      for (int k = 0; k < RK; ++k) {
+        const float bv = tile[tid * RP + k];
+        float qv[MQ];
+        if constexpr (MQ >= 4) {
+#pragma unroll
+          for (int u = 0; u < MQ / 4; ++u) {
+            const float4 t = *(const float4*)(qs + k * FEW_MAX + 4 * u);
+            qv[4 * u] = t.x; qv[4 * u + 1] = t.y; qv[4 * u + 2] = t.z; qv[4 * u + 3] = t.w;
+          }
+        } else if constexpr (MQ == 2) {
+          const float2 t = *(const float2*)(qs + k * FEW_MAX);
+          qv[0] = t.x; qv[1] = t.y;
+        } else {
+          qv[0] = qs[k * FEW_MAX];
+        }
+#pragma unroll
+        for (int i = 0; i < MQ; ++i) acc[i] = fmaf(qv[i], bv, acc[i]);
+      }
+      __syncthreads();
+    }
+    const int j = j0 + tid;
+    if (j < N) {
+#pragma unroll
+      for (int i = 0; i < MQ; ++i) {
+        if (i < M) {
+          const float s = acc[i];
+          if (sim) sim[(long)i * N + j] = s;
+          const tk_entry_t e = tk_pack(s, j);
+          if (cnt[i] < K || e > list[i * K + K - 1]) cand[i * FR + atomicAdd(&ncand[i], 1)] = e;  // <= FR rows of this block per query
+        }
+      }
+    }
+    __syncthreads();
+    // fold the candidates in, 64 at a time: wave w takes the queries w, w + 2, ... (the same trip count for both waves)
+    int maxnc = 0;
+#pragma unroll
+    for (int i = 0; i < MQ; ++i) maxnc = max(maxnc, ncand[i]);
+    for (int c0 = 0; c0 < maxnc; c0 += 64) {
+      for (int i0 = 0; i0 < MQ; i0 += FR / 64) {
+        const bool on = i0 + wave < MQ;
+        const int i = on ? i0 + wave : 0;
+        const int nc = on ? min(64, max(0, ncand[i] - c0)) : 0, n = cnt[i];
+        tk_entry_t* L = list + i * K;
+        TkFold f;
+        f.read(L, n, cand + i * FR + c0, nc, lane);
+        __syncthreads();
+        if (nc) {
+          f.place(L, K);
+          if (lane == 0) cnt[i] = min(K, n + nc);
+        }
+      }
+      __syncthreads();
+    }
+    if (maxnc && tid < MQ) ncand[tid] = 0;  // (the next block's chunk loop has barriers before the next candidate)
+  }
+  __syncthreads();
+  for (int e = tid; e < M * K; e += FR) {
+    const int i = e / K, r = e - i * K;
+    const tk_entry_t v = list[e];
+    if (S == 1) {
+      idx_out[e] = (int)(unsigned)v;
+      score_out[e] = tk_score(v);
+    } else {
+      part[((long)i * S + blockIdx.x) * K + r] = v;
+    }
+  }
+}
+
+// grid (groups, M): the lists [g FEW_G, g FEW_G + ns) of in [M][S][K] -> list g of out [M][S_out][K], or (FINAL, one group) idx / score
+template <bool FINAL>
+__global__ __launch_bounds__(FEW_MT) void rt_few_merge_kernel(const tk_entry_t* in, int S, int K, tk_entry_t* out, int S_out, int* idx_out,
+                                                           float* score_out) {
+  extern __shared__ __attribute__((aligned(16))) char few_lds[];
+  tk_entry_t* P = (tk_entry_t*)few_lds;  // [ns][K]
+  const int tid = threadIdx.x, g = blockIdx.x, q = blockIdx.y;
+  const int s0 = g * FEW_G, ns = min(FEW_G, S - s0);
+  const tk_entry_t* src = in + ((long)q * S + s0) * K;
+  for (int e = tid; e < ns * K; e += FEW_MT) P[e] = src[e];
+  __syncthreads();
+  for (int e = tid; e < ns * K; e += FEW_MT) {
+    const int s = e / K;
+    const tk_entry_t v = P[e];
+    int rank = e - s * K;
+    for (int t = 0; t < ns && rank < K; ++t)
+      if (t != s) rank += tk_ahead(P + t * K, K, v);
+    if (rank < K) {
+      if (FINAL) {  // (an unfilled slot is behind all N >= K real entries)
+        idx_out[(long)q * K + rank] = (int)(unsigned)v;
+        score_out[(long)q * K + rank] = tk_score(v);
+      } else {
+        out[((long)q * S_out + g) * K + rank] = v;
+      }
+    }
+  }
+}
+
+// row splits and the 128-row blocks each one sweeps: every split has at least one block.  cap bounds S whatever the option says:
+// the workspace is sized by it, so it does not depend on the option and stops growing with N.
+struct FewPlan { int MQ, S, blocks, cap; };
+FewPlan few_plan(int M, int N) {
+  FewPlan p;
+  p.MQ = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : M <= 8 ? 8 : 16;
+  const int nb = (N + FR - 1) / FR;
+  p.cap = nb < FEW_SMAX ? nb : FEW_SMAX;
+  int S = g_rt_few_splits > 0 ? g_rt_few_splits : p.cap;
+  S = S > p.cap ? p.cap : S;
+  p.blocks = (nb + S - 1) / S; p.S = (nb + p.blocks - 1) / p.blocks;
+  return p;
+}
+struct FewWs { float *qnorm, *qn; tk_entry_t *part_a, *part_b; size_t bytes; };
+FewWs few_layout(void* base, int M, int d, int K, int cap) {
+  FewWs w; size_t off = 0;
+  auto take = [&](size_t n) { char* p = base ? (char*)base + off : nullptr; off += (n + 255) & ~(size_t)255; return (void*)p; };
+  const int dpad = (d + RK - 1) / RK * RK;
+  w.qnorm = (float*)take((size_t)FEW_MAX * 4); w.qn = (float*)take((size_t)dpad * FEW_MAX * 4);
+  w.part_a = (tk_entry_t*)take(cap > 1 ? (size_t)M * cap * K * 8 : 0);
+  w.part_b = (tk_entry_t*)take(cap > FEW_G ? (size_t)M * ((cap + FEW_G - 1) / FEW_G) * K * 8 : 0);
+  w.bytes = off;
+  return w;
+}
+
+template <int MQ>
+void few_launch(const FewPlan& p, const FewWs& w, const float* gallery, const float* gallery_norms, int M, int N, int d, int K, int32_t* idx_out,
+                float* score_out, float* sim_out, hipStream_t st) {
+  const int vec = d % 4 == 0 && ((uintptr_t)gallery & 15) == 0;
+  const size_t lds = few_lds_bytes(MQ, K);
+  if (gallery_norms)
+    hipLaunchKernelGGL((rt_few_kernel<MQ, true>), dim3(p.S), dim3(FR), lds, st, gallery, gallery_norms, (const float*)w.qn, M, N, d, K, p.blocks, p.S,
+                       vec, sim_out, w.part_a, (int*)idx_out, score_out);
+  else
+    hipLaunchKernelGGL((rt_few_kernel<MQ, false>), dim3(p.S), dim3(FR), lds, st, gallery, (const float*)nullptr, (const float*)w.qn, M, N, d, K,
+                       p.blocks, p.S, vec, sim_out, w.part_a, (int*)idx_out, score_out);
 }
 
 // ---- labelled ranking: M queries, N gallery rows, labels[i] = the gallery row of query i (coot_retrieval_ranks_labeled) ------
@@ -617,6 +866,8 @@ LabWs lab_layout(void* base, int M, int N) {
 }  // namespace
 void set_rt_topk_splits(int n) { g_rt_topk_splits = n; }
 int get_rt_topk_splits() { return g_rt_topk_splits; }
+void set_rt_few_splits(int n) { g_rt_few_splits = n; }
+int get_rt_few_splits() { return g_rt_few_splits; }
 }  // namespace coot
 
 using namespace coot;
@@ -717,6 +968,55 @@ int coot_retrieval_topk(const float* queries, const float* gallery, int M, int N
     hipLaunchKernelGGL(rt_topk_merge_kernel, dim3((M + 3) / 4), dim3(256), 0, st, (const tk_entry_t*)w.part, M, sp.S, K, (int*)idx_out, score_out);
     COOT_CHECK_LAUNCH("rt_topk_merge");
   }
+  return 0;
+}
+
+int coot_retrieval_row_norms(const float* rows, int N, int d, float* norms, coot_stream_t stream) {
+  COOT_REQUIRE(rows && norms, "retrieval_row_norms: null pointer");
+  COOT_REQUIRE(N >= 1 && d >= 1, "retrieval_row_norms: N = %d, d = %d", N, d);
+  hipLaunchKernelGGL(rt_norms_kernel, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, rows, N, (const float*)nullptr, 0, d, norms, (float*)nullptr);
+  COOT_CHECK_LAUNCH("rt_norms");
+  return 0;
+}
+
+size_t coot_retrieval_topk_few_workspace_bytes(int M, int N, int d, int K) {
+  if (M < 1 || N < 1 || d < 1 || K < 1) return 256;
+  return few_layout(nullptr, M, d, K, few_plan(M, N).cap).bytes + 256;
+}
+
+int coot_retrieval_topk_few(const float* queries, const float* gallery, const float* gallery_norms, int M, int N, int d, int K, int32_t* idx_out,
+                            float* score_out, float* sim_out, void* workspace, size_t workspace_bytes, coot_stream_t stream) {
+  COOT_REQUIRE(queries && gallery && idx_out && score_out && workspace, "retrieval_topk_few: null pointer");
+  COOT_REQUIRE(M >= 1 && M <= FEW_MAX && N >= 1 && d >= 1, "retrieval_topk_few: M = %d (1 .. %d), N = %d, d = %d", M, FEW_MAX, N, d);
+  COOT_REQUIRE(K >= 1 && K <= N && K <= TK_MAX, "retrieval_topk_few: K = %d is outside 1 .. min(N = %d, %d)", K, N, TK_MAX);
+  COOT_REQUIRE(((uintptr_t)workspace & 15) == 0, "retrieval_topk_few: workspace is not 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const FewPlan p = few_plan(M, N);
+  const FewWs w = few_layout(workspace, M, d, K, p.cap);
+  COOT_REQUIRE(w.bytes <= workspace_bytes, "retrieval_topk_few: workspace too small (%zu < %zu)", workspace_bytes, w.bytes);
+  hipLaunchKernelGGL(rt_few_prep_kernel, dim3(FEW_MAX), dim3(64), 0, st, queries, M, d, (d + RK - 1) / RK * RK, gallery_norms != nullptr, w.qnorm, w.qn);
+  COOT_CHECK_LAUNCH("rt_few_prep");
+  switch (p.MQ) {
+    case 1: few_launch<1>(p, w, gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, st); break;
+    case 2: few_launch<2>(p, w, gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, st); break;
+    case 4: few_launch<4>(p, w, gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, st); break;
+    case 8: few_launch<8>(p, w, gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, st); break;
+    default: few_launch<16>(p, w, gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, st); break;
+  }
+  COOT_CHECK_LAUNCH("rt_few");
+  if (p.S == 1) return 0;
+  // merge by rank in rounds of <= FEW_G lists, the two list buffers taking turns
+  const tk_entry_t* cur = w.part_a;
+  tk_entry_t* nxt = w.part_b;
+  int S = p.S;
+  while (S > FEW_G) {
+    const int So = (S + FEW_G - 1) / FEW_G;
+    hipLaunchKernelGGL(rt_few_merge_kernel<false>, dim3(So, M), dim3(FEW_MT), (size_t)FEW_G * K * 8, st, cur, S, K, nxt, So, (int*)nullptr, (float*)nullptr);
+    COOT_CHECK_LAUNCH("rt_few_merge");
+    tk_entry_t* done = nxt; nxt = (tk_entry_t*)cur; cur = done; S = So;
+  }
+  hipLaunchKernelGGL(rt_few_merge_kernel<true>, dim3(1, M), dim3(FEW_MT), (size_t)S * K * 8, st, cur, S, K, (tk_entry_t*)nullptr, 1, (int*)idx_out, score_out);
+  COOT_CHECK_LAUNCH("rt_few_merge");
   return 0;
 }
 

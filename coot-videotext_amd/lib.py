@@ -32,6 +32,7 @@ EXPORTS = [
     "coot_adam_step", "coot_radam_step", "coot_step_update", "coot_step_set_global_done_events", "coot_step_device_state_bytes", "coot_step_set_device_state", "coot_step_loss_scaler_bytes", "coot_step_set_loss_scaler", "coot_step_unscale_grads", "coot_step_grad_clip_bytes", "coot_step_set_grad_clip", "coot_step_grad_norm", "coot_collate_level", "coot_collate_packed", "coot_sample_cycle_indices", "coot_step_set_cycle_indices", "coot_step_input_stage_bytes", "coot_step_set_input_stages", "coot_step_set_next_batch", "coot_contrastive_fwd_bwd_dp", "coot_contrastive_fwd_bwd_dp_blocks", "coot_retrieval_workspace_bytes", "coot_retrieval_ranks", "coot_retrieval_topk_workspace_bytes", "coot_retrieval_topk",
     "coot_retrieval_ranks_part_workspace_bytes", "coot_retrieval_ranks_part", "coot_retrieval_metrics",
     "coot_retrieval_ranks_labeled_workspace_bytes", "coot_retrieval_ranks_labeled",
+    "coot_retrieval_row_norms", "coot_retrieval_topk_few_workspace_bytes", "coot_retrieval_topk_few",
     "coot_det_shadow_bytes", "coot_det_configure", "coot_det_flush", "coot_event_record", "coot_event_wait", "coot_event_handle", "coot_stream_hop",
     "coot_stream_create_concurrent", "coot_stream_destroy", "coot_streams_overlap",
 ]
@@ -189,6 +190,10 @@ def load():
     lib.coot_retrieval_topk_workspace_bytes.argtypes = [i32, i32, i32, i32]
     lib.coot_retrieval_topk_workspace_bytes.restype = C.c_size_t
     lib.coot_retrieval_topk.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.coot_retrieval_row_norms.argtypes = [vp, i32, i32, vp, vp]
+    lib.coot_retrieval_topk_few_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    lib.coot_retrieval_topk_few_workspace_bytes.restype = C.c_size_t
+    lib.coot_retrieval_topk_few.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, C.c_size_t, vp]
     lib.coot_retrieval_ranks_labeled_workspace_bytes.argtypes = [i32, i32, i32]
     lib.coot_retrieval_ranks_labeled_workspace_bytes.restype = C.c_size_t
     lib.coot_retrieval_ranks_labeled.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]

@@ -8,7 +8,8 @@ in four launches, the N x N matrix is never materialised).  No CPU 
 
 compute_retrieval_topk / retrieval_topk_device: WHICH gallery items a query retrieves (the reference returns top1 only), for M
 queries against N gallery rows, M and N independent: the host mirror on a similarity matrix, and coot_retrieval_topk on the
-device (similarities and selection fused, no M x N matrix).
+device (similarities and selection fused, no M x N matrix).  GalleryIndex: the same search for a few queries at a time on a
+gallery that stays on the device, its row norms computed once (coot_retrieval_topk_few: the same bytes, one sweep of the gallery).
 
 Sharded validation (data-parallel runs): retrieval_ranks_part_device counts one strip of rows, an integer all-reduce of the
 strips is the whole (compute_retrieval_device(dp=...)), retrieval_metrics_device turns rank vectors into the metrics;
@@ -102,6 +103,67 @@ def retrieval_topk_device(queries, gallery, k: int, normalize: bool = False, wan
                                        sim.data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(),
                                        torch.cuda.current_stream().cuda_stream), "coot_retrieval_topk")
     return idx, scores, sim
+
+
+RETRIEVAL_FEW_MAX = 16  # include/coot_hip.h: COOT_RETRIEVAL_FEW_MAX
+
+
+class GalleryIndex:
+    """A gallery that stays on the device between searches: a few queries at a time against a corpus that does not change.
+
+    GalleryIndex(gallery, normalize=True): gallery is a cuda float32 [N, d] tensor, kept by reference when contiguous (a copy
+    otherwise).  normalize=True computes the row norms once (coot_retrieval_row_norms) and every search divides by them, as
+    retrieval_topk_device(normalize=True) does.  The index does not watch the tensor: a caller that changes the gallery builds a
+    new index, or searches with stale norms.
+
+    search(queries, k, want_sim=False) returns (idx int32 [M, k], scores float32 [M, k], sim [M, N] or None) on the device, no
+    synchronisation: the bytes of retrieval_topk_device(queries, gallery, k, normalize=...).  M <= RETRIEVAL_FEW_MAX goes through
+    coot_retrieval_topk_few with the stored norms: one sweep of the gallery, one row per thread.  M > RETRIEVAL_FEW_MAX goes through
+    retrieval_topk_device unchanged, which recomputes the gallery norms on every call.  queries [d] is one query.
+    1 <= k <= min(N, 128)."""
+
+    def __init__(self, gallery, normalize: bool = True):
+        import torch
+        from . import lib as _lib
+        if not gallery.is_cuda:
+            raise RuntimeError("GalleryIndex needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk)")
+        assert gallery.dtype == torch.float32 and gallery.dim() == 2 and gallery.shape[0] >= 1 and gallery.shape[1] >= 1, (gallery.dtype, gallery.shape)
+        self.gallery = gallery.contiguous()
+        self.normalize = bool(normalize)
+        self.norms = None
+        if self.normalize:
+            n, d = self.gallery.shape
+            self.norms = torch.empty(n, dtype=torch.float32, device=gallery.device)
+            _lib.check(_lib.load().coot_retrieval_row_norms(self.gallery.data_ptr(), n, d, self.norms.data_ptr(),
+                                                            torch.cuda.current_stream().cuda_stream), "coot_retrieval_row_norms")
+
+    def search(self, queries, k: int, want_sim: bool = False):
+        import torch
+        from . import lib as _lib
+        if not queries.is_cuda:
+            raise RuntimeError("GalleryIndex.search needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk)")
+        if queries.dim() == 1:
+            queries = queries[None]
+        (n, d), k = self.gallery.shape, int(k)
+        assert queries.dtype == torch.float32 and queries.dim() == 2, (queries.dtype, queries.shape)
+        if queries.shape[1] != d:
+            raise ValueError(f"GalleryIndex.search: queries of width {queries.shape[1]}, gallery of width {d}")
+        if not 1 <= k <= min(n, 128):
+            raise ValueError(f"GalleryIndex.search: k = {k} is outside 1 .. min(N = {n}, 128)")
+        m = queries.shape[0]
+        if m > RETRIEVAL_FEW_MAX:
+            return retrieval_topk_device(queries, self.gallery, k, normalize=self.normalize, want_sim=want_sim)
+        queries = queries.contiguous()
+        lib = _lib.load()
+        dev = queries.device
+        ws = torch.empty(lib.coot_retrieval_topk_few_workspace_bytes(m, n, d, k), dtype=torch.uint8, device=dev)
+        idx = torch.empty(m, k, dtype=torch.int32, device=dev)
+        scores = torch.empty(m, k, dtype=torch.float32, device=dev)
+        sim = torch.empty(m, n, dtype=torch.float32, device=dev) if want_sim else None
+        _lib.check(lib.coot_retrieval_topk_few(queries.data_ptr(), self.gallery.data_ptr(), self.norms.data_ptr() if self.normalize else None,
+                                               m, n, d, k, idx.data_ptr(), scores.data_ptr(), sim.data_ptr() if want_sim else None,
+                                               ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream), "coot_retrieval_topk_few")
+        return idx, scores, sim
 
 
 def _ahead(s, idx, t, a):

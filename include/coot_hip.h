@@ -358,6 +358,29 @@ size_t coot_retrieval_topk_workspace_bytes(int M, int N, int d, int K);
 int coot_retrieval_topk(const float* queries, const float* gallery, int M, int N, int d, int K, int normalize, int32_t* idx_out,
                         float* score_out, float* sim_out, void* workspace, size_t workspace_bytes, coot_stream_t stream);
 
+/* ---- the same search for a few queries on a prepared gallery (low latency) ---------------------------------------------
+ * How a trained model is used: one paragraph, or a handful, against a corpus that stays in device memory between calls.
+ * coot_retrieval_row_norms writes norms[j] = sqrt(sum x^2) of every row of rows [N, d]: exactly the divisor normalize != 0 uses
+ * in the calls above.  It is the "prepared" part: the caller computes it once per gallery and owns the buffer (the library
+ * retains no pointer); a gallery that changes needs its norms again.
+ * coot_retrieval_topk_few: 1 <= M <= COOT_RETRIEVAL_FEW_MAX queries, 1 <= K <= min(N, 128).  idx_out, score_out [M, K] and the
+ * optional sim_out [M, N] (testing aid) are byte for byte what coot_retrieval_topk writes for the same inputs, with
+ *   gallery_norms != NULL: normalize = 1; the query norms are computed inside the call, the gallery's are taken as given;
+ *   gallery_norms == NULL: normalize = 0, rows used as they are.
+ * One gallery row per thread and one accumulator per query instead of 64 x 64 tiles: the same fp32 FMA chain per element (k order,
+ * chunks of 32), the same total order in selection and merge, so the result does not depend on the row split or the schedule
+ * (coot_set_option("rt_few_splits", n) fixes the number of row splits for tests, 0 = automatic; the workspace size does not
+ * depend on it).  The gallery is read once per call.  workspace (16-byte aligned): coot_retrieval_topk_few_workspace_bytes =
+ * the query norms, the normalised queries [d rounded up to 32, 16] and the partial lists, M x splits x K 64-bit words (+ 1/32 of
+ * that for the merge rounds), splits <= min(ceil(N / 128), 1024): it does not grow with N beyond 131 072 rows.
+ * A refused call (null pointer, M or K outside its range, workspace too small) writes nothing.  No allocation, no synchronisation. */
+#define COOT_RETRIEVAL_FEW_MAX 16
+int coot_retrieval_row_norms(const float* rows, int N, int d, float* norms, coot_stream_t stream);
+size_t coot_retrieval_topk_few_workspace_bytes(int M, int N, int d, int K);
+int coot_retrieval_topk_few(const float* queries, const float* gallery, const float* gallery_norms, int M, int N, int d, int K,
+                            int32_t* idx_out, float* score_out, float* sim_out, void* workspace, size_t workspace_bytes,
+                            coot_stream_t stream);
+
 /* ---- labelled retrieval ranking on the device: M queries, N gallery rows, several queries per row -----------------------
  * coot_retrieval_ranks without the assumption "N x N, ground truth on the diagonal": labels[i] (device int32 [M]) is the gallery
  * row of query i.  Several queries may share a row (a second annotation set, several captions per clip), rows may have no query
