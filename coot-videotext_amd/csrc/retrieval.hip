@@ -24,10 +24,23 @@ constexpr int RT = 64;   // tile: 64 rows of emb1 x 64 rows of emb2
 constexpr int RK = 32;   // k chunk
 constexpr int RP = RK + 1;
 
+// A gallery element as fp32: itself, a bfloat16 (unsigned short: the upper half of the fp32 word) or an IEEE half (v_cvt_f32_f16).
+// Both 16-bit formats widen exactly, so whatever follows sees the operands of the widened fp32 copy.
+__device__ __forceinline__ float widen(float x) { return x; }
+__device__ __forceinline__ float widen(unsigned short x) { return __uint_as_float((unsigned)x << 16); }
+__device__ __forceinline__ float widen(_Float16 x) { return (float)x; }
+// half e (0 = low) of a 32-bit word that holds two 16-bit elements
+template <typename T>
+__device__ __forceinline__ float widen_half(unsigned w, int e) {
+  const unsigned short b = (unsigned short)(e ? w >> 16 : w & 0xFFFFu);
+  return widen(__builtin_bit_cast(T, b));
+}
+
 // sum x^2 of one row by one wave: the norm of rt_normalize_kernel and of rt_norms_kernel is this sum's sqrtf
-__device__ __forceinline__ float row_sumsq(const float* src, int d, int lane) {
+template <typename T>
+__device__ __forceinline__ float row_sumsq(const T* src, int d, int lane) {
   float s = 0.f;
-  for (int c = lane; c < d; c += 64) { const float x = src[c]; s += x * x; }
+  for (int c = lane; c < d; c += 64) { const float x = widen(src[c]); s += x * x; }
   return wave_sum(s);
 }
 
@@ -387,8 +400,9 @@ __global__ __launch_bounds__(256) void rt_topk_merge_kernel(const tk_entry_t* pa
   }
 }
 
-// sqrt(sum x^2) of every row of a [Ma, d], then of b [Nb, d]: rt_normalize_kernel's divisor
-__global__ __launch_bounds__(256) void rt_norms_kernel(const float* a, int Ma, const float* b, int Nb, int d, float* na, float* nb) {
+// sqrt(sum x^2) of every row of a [Ma, d], then of b [Nb, d]: rt_normalize_kernel's divisor (T: fp32 rows, or 16-bit rows widened)
+template <typename T>
+__global__ __launch_bounds__(256) void rt_norms_kernel(const T* a, int Ma, const T* b, int Nb, int d, float* na, float* nb) {
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= Ma + Nb) return;
   const float s = row_sumsq(row < Ma ? a + (long)row * d : b + (long)(row - Ma) * d, d, lane);
@@ -430,6 +444,11 @@ TkWs tk_layout(void* base, int M, int N, int K, int S) {
 //   rt_few_merge_kernel: rt_topk_merge_kernel's merge by rank over <= 32 lists held in LDS, one workgroup of 1 024 threads per (group, query); a
 //     round writes entry lists again (782 lists -> 25 -> the result), the last one idx / score.  Unfilled slots (0) rank behind
 //     every entry and land on the unfilled slots of the merged list, so short lists (K > rows of a workgroup) pass through.
+// A gallery stored in bfloat16 or IEEE half (coot_retrieval_topk_few_h): rt_few_kernel on that element type.  Only the global load
+// and the widening at staging differ — 16 bytes are 8 elements, a chunk of a block is 4 loads per thread — and a widened element is
+// the fp32 value of the widened copy, so the tile, the chain and everything after it are the fp32 sweep's and so are the bytes.
+// One chunk is in flight under the FMAs, as in the fp32 sweep, and it is half the bytes: whether two chunks in flight pay for their
+// registers has not been timed.
 constexpr int FEW_MAX = COOT_RETRIEVAL_FEW_MAX;  // queries
 constexpr int FR = 128;                          // gallery rows per step = threads per workgroup
 constexpr int FEW_SMAX = 1024;                   // row splits: about four workgroups per CU
@@ -453,9 +472,35 @@ __global__ __launch_bounds__(64) void rt_few_prep_kernel(const float* q, int M, 
 
 size_t few_lds_bytes(int MQ, int K) { return (size_t)(FR * RP + RK * FEW_MAX) * 4 + (size_t)MQ * K * 8 + 2 * FEW_MAX * 4; }
 
+// one chunk of the chain for the thread's gallery row: acc[i] = fmaf(q_ik, g_jk, acc[i]) over the chunk's 32 k in order.  The 16-bit
+// sweep calls it; the fp32 sweep keeps the same loop in its body, so that its instantiations compile to the instructions they had
+template <int MQ>
+__device__ __forceinline__ void few_fma_chunk(const float* tile, const float* qs, int tid, float (&acc)[MQ]) {
+#pragma unroll 4
+  for (int k = 0; k < RK; ++k) {
+    const float bv = tile[tid * RP + k];
+    float qv[MQ];
+    if constexpr (MQ >= 4) {
+#pragma unroll
+      for (int u = 0; u < MQ / 4; ++u) {
+        const float4 t = *(const float4*)(qs + k * FEW_MAX + 4 * u);
+        qv[4 * u] = t.x; qv[4 * u + 1] = t.y; qv[4 * u + 2] = t.z; qv[4 * u + 3] = t.w;
+      }
+    } else if constexpr (MQ == 2) {
+      const float2 t = *(const float2*)(qs + k * FEW_MAX);
+      qv[0] = t.x; qv[1] = t.y;
+    } else {
+      qv[0] = qs[k * FEW_MAX];
+    }
+#pragma unroll
+    for (int i = 0; i < MQ; ++i) acc[i] = fmaf(qv[i], bv, acc[i]);
+  }
+}
+
 // grid (S); MQ = M rounded up to 1, 2, 4, 8, 16 accumulators; LDS: tile [FR][RP] | qs [RK][16] | list [MQ][K] | cnt | ncand
-template <int MQ, bool NORM>
-__global__ __launch_bounds__(FR) void rt_few_kernel(const float* __restrict__ G, const float* __restrict__ gnorm, const float* __restrict__ qn, int M,
+// GT: the gallery's element type, float, unsigned short (bfloat16) or _Float16
+template <typename GT, int MQ, bool NORM>
+__global__ __launch_bounds__(FR) void rt_few_kernel(const GT* __restrict__ G, const float* __restrict__ gnorm, const float* __restrict__ qn, int M,
                                                     int N, int d, int K, int blocks_per_split, int S, int vec, float* __restrict__ sim,
                                                     tk_entry_t* __restrict__ part, int* __restrict__ idx_out, float* __restrict__ score_out) {
   extern __shared__ __attribute__((aligned(16))) char few_lds[];
@@ -468,70 +513,123 @@ __global__ __launch_bounds__(FR) void rt_few_kernel(const float* __restrict__ G,
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int nb = (N + FR - 1) / FR, nchunks = (d + RK - 1) / RK;
   const int b0 = blockIdx.x * blocks_per_split, b1 = min(nb, b0 + blocks_per_split);
-  const int sr = tid >> 3, sk = (tid & 7) * 4;  // staging: floats sk .. sk + 3 of the rows sr + 16 q of a chunk
   if (tid < FEW_MAX) { cnt[tid] = 0; ncand[tid] = 0; }
   for (int e = tid; e < MQ * K; e += FR) list[e] = 0ull;  // 0 = behind every entry: an unfilled slot
   for (int b = b0; b < b1; ++b) {
     const int j0 = b * FR;
-    float rb[8];
-    if (NORM) {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) rb[q] = j0 + sr + 16 * q < N ? gnorm[j0 + sr + 16 * q] : 1.f;
-    }
-    float4 pf[8], pq;
-    // one chunk into registers: 8 x 16 bytes of the gallery and 16 of the table per thread.  No branch: an address beyond N or d
-    // is clamped into the gallery and its value is dropped at staging
-    auto load = [&](int k0) {
-      const int k = k0 + sk;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const float* p = G + (long)min(j0 + sr + 16 * q, N - 1) * d;
-        if (vec) {
-          pf[q] = *(const float4*)(p + (k < d ? k : 0));
-        } else {
-          pf[q].x = p[min(k, d - 1)]; pf[q].y = p[min(k + 1, d - 1)]; pf[q].z = p[min(k + 2, d - 1)]; pf[q].w = p[min(k + 3, d - 1)];
-        }
-      }
-      pq = *(const float4*)(qn + (long)k0 * FEW_MAX + tid * 4);
-    };
     float acc[MQ];
+    if constexpr (sizeof(GT) == 4) {
+      const int sr = tid >> 3, sk = (tid & 7) * 4;  // staging: floats sk .. sk + 3 of the rows sr + 16 q of a chunk
+      float rb[8];
+      if (NORM) {
 #pragma unroll
-    for (int i = 0; i < MQ; ++i) acc[i] = 0.f;
-    load(0);
-    for (int c = 0; c < nchunks; ++c) {
-      const int k0 = c * RK;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int r = sr + 16 * q;
-        const bool rin = j0 + r < N;
-        const float v[4] = {pf[q].x, pf[q].y, pf[q].z, pf[q].w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e)  // rows beyond N and columns beyond d are zero, as tile_dot stages them
-          tile[r * RP + sk + e] = (rin && k0 + sk + e < d) ? (NORM ? v[e] / rb[q] : v[e]) : 0.f;
+        for (int q = 0; q < 8; ++q) rb[q] = j0 + sr + 16 * q < N ? gnorm[j0 + sr + 16 * q] : 1.f;
       }
-      *(float4*)(qs + tid * 4) = pq;
-      __syncthreads();
-      if (c + 1 < nchunks) load(k0 + RK);  // in flight under the FMAs
-#pragma unroll 4
-      for (int k = 0; k < RK; ++k) {
-        const float bv = tile[tid * RP + k];
-        float qv[MQ];
-        if constexpr (MQ >= 4) {
+      float4 pf[8], pq;
+      // one chunk into registers: 8 x 16 bytes of the gallery and 16 of the table per thread.  No branch: an address beyond N or d
+      // is clamped into the gallery and its value is dropped at staging
+      auto load = [&](int k0) {
+        const int k = k0 + sk;
 #pragma unroll
-          for (int u = 0; u < MQ / 4; ++u) {
-            const float4 t = *(const float4*)(qs + k * FEW_MAX + 4 * u);
-            qv[4 * u] = t.x; qv[4 * u + 1] = t.y; qv[4 * u + 2] = t.z; qv[4 * u + 3] = t.w;
+        for (int q = 0; q < 8; ++q) {
+          const float* p = G + (long)min(j0 + sr + 16 * q, N - 1) * d;
+          if (vec) {
+            pf[q] = *(const float4*)(p + (k < d ? k : 0));
+          } else {
+            pf[q].x = p[min(k, d - 1)]; pf[q].y = p[min(k + 1, d - 1)]; pf[q].z = p[min(k + 2, d - 1)]; pf[q].w = p[min(k + 3, d - 1)];
           }
-        } else if constexpr (MQ == 2) {
-          const float2 t = *(const float2*)(qs + k * FEW_MAX);
-          qv[0] = t.x; qv[1] = t.y;
-        } else {
-          qv[0] = qs[k * FEW_MAX];
         }
+        pq = *(const float4*)(qn + (long)k0 * FEW_MAX + tid * 4);
+      };
 #pragma unroll
-        for (int i = 0; i < MQ; ++i) acc[i] = fmaf(qv[i], bv, acc[i]);
+      for (int i = 0; i < MQ; ++i) acc[i] = 0.f;
+      load(0);
+      for (int c = 0; c < nchunks; ++c) {
+        const int k0 = c * RK;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const int r = sr + 16 * q;
+          const bool rin = j0 + r < N;
+          const float v[4] = {pf[q].x, pf[q].y, pf[q].z, pf[q].w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e)  // rows beyond N and columns beyond d are zero, as tile_dot stages them
+            tile[r * RP + sk + e] = (rin && k0 + sk + e < d) ? (NORM ? v[e] / rb[q] : v[e]) : 0.f;
+        }
+        *(float4*)(qs + tid * 4) = pq;
+        __syncthreads();
+        if (c + 1 < nchunks) load(k0 + RK);  // in flight under the FMAs
+#pragma unroll 4
+        for (int k = 0; k < RK; ++k) {
+          const float bv = tile[tid * RP + k];
+          float qv[MQ];
+          if constexpr (MQ >= 4) {
+#pragma unroll
+            for (int u = 0; u < MQ / 4; ++u) {
+              const float4 t = *(const float4*)(qs + k * FEW_MAX + 4 * u);
+              qv[4 * u] = t.x; qv[4 * u + 1] = t.y; qv[4 * u + 2] = t.z; qv[4 * u + 3] = t.w;
+            }
+          } else if constexpr (MQ == 2) {
+            const float2 t = *(const float2*)(qs + k * FEW_MAX);
+            qv[0] = t.x; qv[1] = t.y;
+          } else {
+            qv[0] = qs[k * FEW_MAX];
+          }
+#pragma unroll
+          for (int i = 0; i < MQ; ++i) acc[i] = fmaf(qv[i], bv, acc[i]);
+        }
+        __syncthreads();
       }
-      __syncthreads();
+    } else {
+      // 16-bit storage: 16 bytes are 8 elements, so a chunk is 4 loads per thread, elements sk .. sk + 7 of the rows sr + 32 q.  The
+      // same clamping and the same zeros; an element is widened when it is staged and the fp32 tile is the one above
+      const int sr = tid >> 2, sk = (tid & 3) * 8;
+      float rb[4];
+      if (NORM) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) rb[q] = j0 + sr + 32 * q < N ? gnorm[j0 + sr + 32 * q] : 1.f;
+      }
+      auto load = [&](int k0, uint4 (&pf)[4], float4& pq) {
+        const int k = k0 + sk;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const unsigned short* p = (const unsigned short*)(G + (long)min(j0 + sr + 32 * q, N - 1) * d);
+          if (vec) {  // d % 8 == 0: k < d leaves 8 elements in the row
+            pf[q] = *(const uint4*)(p + (k < d ? k : 0));
+          } else {
+            unsigned w[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) w[e] = (unsigned)p[min(k + 2 * e, d - 1)] | (unsigned)p[min(k + 2 * e + 1, d - 1)] << 16;
+            pf[q] = make_uint4(w[0], w[1], w[2], w[3]);
+          }
+        }
+        pq = *(const float4*)(qn + (long)k0 * FEW_MAX + tid * 4);
+      };
+      auto stage = [&](int k0, const uint4 (&pf)[4], const float4& pq) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int r = sr + 32 * q;
+          const bool rin = j0 + r < N;
+          const unsigned w[4] = {pf[q].x, pf[q].y, pf[q].z, pf[q].w};
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float v = widen_half<GT>(w[e >> 1], e & 1);
+            tile[r * RP + sk + e] = (rin && k0 + sk + e < d) ? (NORM ? v / rb[q] : v) : 0.f;
+          }
+        }
+        *(float4*)(qs + tid * 4) = pq;
+      };
+#pragma unroll
+      for (int i = 0; i < MQ; ++i) acc[i] = 0.f;
+      uint4 pf[4];
+      float4 pq;
+      load(0, pf, pq);
+      for (int c = 0; c < nchunks; ++c) {
+        stage(c * RK, pf, pq);
+        __syncthreads();
+        if (c + 1 < nchunks) load((c + 1) * RK, pf, pq);  // in flight under the FMAs
+        few_fma_chunk<MQ>(tile, qs, tid, acc);
+        __syncthreads();
+      }
     }
     const int j = j0 + tid;
     if (j < N) {
@@ -634,17 +732,54 @@ FewWs few_layout(void* base, int M, int d, int K, int cap) {
   return w;
 }
 
-template <int MQ>
-void few_launch(const FewPlan& p, const FewWs& w, const float* gallery, const float* gallery_norms, int M, int N, int d, int K, int32_t* idx_out,
+template <typename GT, int MQ>
+void few_launch(const FewPlan& p, const FewWs& w, const GT* gallery, const float* gallery_norms, int M, int N, int d, int K, int32_t* idx_out,
                 float* score_out, float* sim_out, hipStream_t st) {
-  const int vec = d % 4 == 0 && ((uintptr_t)gallery & 15) == 0;
+  const int vec = d % (16 / (int)sizeof(GT)) == 0 && ((uintptr_t)gallery & 15) == 0;  // every row starts 16-byte aligned
   const size_t lds = few_lds_bytes(MQ, K);
   if (gallery_norms)
-    hipLaunchKernelGGL((rt_few_kernel<MQ, true>), dim3(p.S), dim3(FR), lds, st, gallery, gallery_norms, (const float*)w.qn, M, N, d, K, p.blocks, p.S,
+    hipLaunchKernelGGL((rt_few_kernel<GT, MQ, true>), dim3(p.S), dim3(FR), lds, st, gallery, gallery_norms, (const float*)w.qn, M, N, d, K, p.blocks, p.S,
                        vec, sim_out, w.part_a, (int*)idx_out, score_out);
   else
-    hipLaunchKernelGGL((rt_few_kernel<MQ, false>), dim3(p.S), dim3(FR), lds, st, gallery, (const float*)nullptr, (const float*)w.qn, M, N, d, K,
+    hipLaunchKernelGGL((rt_few_kernel<GT, MQ, false>), dim3(p.S), dim3(FR), lds, st, gallery, (const float*)nullptr, (const float*)w.qn, M, N, d, K,
                        p.blocks, p.S, vec, sim_out, w.part_a, (int*)idx_out, score_out);
+}
+
+// coot_retrieval_topk_few (GT = float) and coot_retrieval_topk_few_h (a 16-bit GT): fn names the entry in a refusal
+template <typename GT>
+int few_search(const char* fn, const float* queries, const GT* gallery, const float* gallery_norms, int M, int N, int d, int K, int32_t* idx_out,
+               float* score_out, float* sim_out, void* workspace, size_t workspace_bytes, hipStream_t st) {
+  COOT_REQUIRE(queries && gallery && idx_out && score_out && workspace, "%s: null pointer", fn);
+  COOT_REQUIRE(M >= 1 && M <= FEW_MAX && N >= 1 && d >= 1, "%s: M = %d (1 .. %d), N = %d, d = %d", fn, M, FEW_MAX, N, d);
+  COOT_REQUIRE(K >= 1 && K <= N && K <= TK_MAX, "%s: K = %d is outside 1 .. min(N = %d, %d)", fn, K, N, TK_MAX);
+  COOT_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: workspace is not 16-byte aligned", fn);
+  const FewPlan p = few_plan(M, N);
+  const FewWs w = few_layout(workspace, M, d, K, p.cap);
+  COOT_REQUIRE(w.bytes <= workspace_bytes, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, w.bytes);
+  hipLaunchKernelGGL(rt_few_prep_kernel, dim3(FEW_MAX), dim3(64), 0, st, queries, M, d, (d + RK - 1) / RK * RK, gallery_norms != nullptr, w.qnorm, w.qn);
+  COOT_CHECK_LAUNCH("rt_few_prep");
+  switch (p.MQ) {
+    case 1: few_launch<GT, 1>(p, w, gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, st); break;
+    case 2: few_launch<GT, 2>(p, w, gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, st); break;
+    case 4: few_launch<GT, 4>(p, w, gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, st); break;
+    case 8: few_launch<GT, 8>(p, w, gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, st); break;
+    default: few_launch<GT, 16>(p, w, gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, st); break;
+  }
+  COOT_CHECK_LAUNCH("rt_few");
+  if (p.S == 1) return 0;
+  // merge by rank in rounds of <= FEW_G lists, the two list buffers taking turns
+  const tk_entry_t* cur = w.part_a;
+  tk_entry_t* nxt = w.part_b;
+  int S = p.S;
+  while (S > FEW_G) {
+    const int So = (S + FEW_G - 1) / FEW_G;
+    hipLaunchKernelGGL(rt_few_merge_kernel<false>, dim3(So, M), dim3(FEW_MT), (size_t)FEW_G * K * 8, st, cur, S, K, nxt, So, (int*)nullptr, (float*)nullptr);
+    COOT_CHECK_LAUNCH("rt_few_merge");
+    tk_entry_t* done = nxt; nxt = (tk_entry_t*)cur; cur = done; S = So;
+  }
+  hipLaunchKernelGGL(rt_few_merge_kernel<true>, dim3(1, M), dim3(FEW_MT), (size_t)S * K * 8, st, cur, S, K, (tk_entry_t*)nullptr, 1, (int*)idx_out, score_out);
+  COOT_CHECK_LAUNCH("rt_few_merge");
+  return 0;
 }
 
 // ---- labelled ranking: M queries, N gallery rows, labels[i] = the gallery row of query i (coot_retrieval_ranks_labeled) ------
@@ -955,7 +1090,7 @@ int coot_retrieval_topk(const float* queries, const float* gallery, int M, int N
   const dim3 grid(sp.S, (M + RT - 1) / RT);
   const size_t lds = tk_lds_bytes(K);
   if (normalize) {
-    hipLaunchKernelGGL(rt_norms_kernel, dim3((M + N + 3) / 4), dim3(256), 0, st, queries, M, gallery, N, d, w.na, w.nb);
+    hipLaunchKernelGGL(rt_norms_kernel<float>, dim3((M + N + 3) / 4), dim3(256), 0, st, queries, M, gallery, N, d, w.na, w.nb);
     COOT_CHECK_LAUNCH("rt_norms");
     hipLaunchKernelGGL(rt_topk_kernel<true>, grid, dim3(256), lds, st, queries, gallery, (const float*)w.na, (const float*)w.nb, M, N, d, K,
                        sp.tiles, sp.S, sim_out, w.part, (int*)idx_out, score_out);
@@ -974,7 +1109,7 @@ int coot_retrieval_topk(const float* queries, const float* gallery, int M, int N
 int coot_retrieval_row_norms(const float* rows, int N, int d, float* norms, coot_stream_t stream) {
   COOT_REQUIRE(rows && norms, "retrieval_row_norms: null pointer");
   COOT_REQUIRE(N >= 1 && d >= 1, "retrieval_row_norms: N = %d, d = %d", N, d);
-  hipLaunchKernelGGL(rt_norms_kernel, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, rows, N, (const float*)nullptr, 0, d, norms, (float*)nullptr);
+  hipLaunchKernelGGL(rt_norms_kernel<float>, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, rows, N, (const float*)nullptr, 0, d, norms, (float*)nullptr);
   COOT_CHECK_LAUNCH("rt_norms");
   return 0;
 }
@@ -986,38 +1121,34 @@ size_t coot_retrieval_topk_few_workspace_bytes(int M, int N, int d, int K) {
 
 int coot_retrieval_topk_few(const float* queries, const float* gallery, const float* gallery_norms, int M, int N, int d, int K, int32_t* idx_out,
                             float* score_out, float* sim_out, void* workspace, size_t workspace_bytes, coot_stream_t stream) {
-  COOT_REQUIRE(queries && gallery && idx_out && score_out && workspace, "retrieval_topk_few: null pointer");
-  COOT_REQUIRE(M >= 1 && M <= FEW_MAX && N >= 1 && d >= 1, "retrieval_topk_few: M = %d (1 .. %d), N = %d, d = %d", M, FEW_MAX, N, d);
-  COOT_REQUIRE(K >= 1 && K <= N && K <= TK_MAX, "retrieval_topk_few: K = %d is outside 1 .. min(N = %d, %d)", K, N, TK_MAX);
-  COOT_REQUIRE(((uintptr_t)workspace & 15) == 0, "retrieval_topk_few: workspace is not 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const FewPlan p = few_plan(M, N);
-  const FewWs w = few_layout(workspace, M, d, K, p.cap);
-  COOT_REQUIRE(w.bytes <= workspace_bytes, "retrieval_topk_few: workspace too small (%zu < %zu)", workspace_bytes, w.bytes);
-  hipLaunchKernelGGL(rt_few_prep_kernel, dim3(FEW_MAX), dim3(64), 0, st, queries, M, d, (d + RK - 1) / RK * RK, gallery_norms != nullptr, w.qnorm, w.qn);
-  COOT_CHECK_LAUNCH("rt_few_prep");
-  switch (p.MQ) {
-    case 1: few_launch<1>(p, w, gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, st); break;
-    case 2: few_launch<2>(p, w, gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, st); break;
-    case 4: few_launch<4>(p, w, gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, st); break;
-    case 8: few_launch<8>(p, w, gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, st); break;
-    default: few_launch<16>(p, w, gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, st); break;
-  }
-  COOT_CHECK_LAUNCH("rt_few");
-  if (p.S == 1) return 0;
-  // merge by rank in rounds of <= FEW_G lists, the two list buffers taking turns
-  const tk_entry_t* cur = w.part_a;
-  tk_entry_t* nxt = w.part_b;
-  int S = p.S;
-  while (S > FEW_G) {
-    const int So = (S + FEW_G - 1) / FEW_G;
-    hipLaunchKernelGGL(rt_few_merge_kernel<false>, dim3(So, M), dim3(FEW_MT), (size_t)FEW_G * K * 8, st, cur, S, K, nxt, So, (int*)nullptr, (float*)nullptr);
-    COOT_CHECK_LAUNCH("rt_few_merge");
-    tk_entry_t* done = nxt; nxt = (tk_entry_t*)cur; cur = done; S = So;
-  }
-  hipLaunchKernelGGL(rt_few_merge_kernel<true>, dim3(1, M), dim3(FEW_MT), (size_t)S * K * 8, st, cur, S, K, (tk_entry_t*)nullptr, 1, (int*)idx_out, score_out);
-  COOT_CHECK_LAUNCH("rt_few_merge");
+  return few_search("retrieval_topk_few", queries, gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, workspace, workspace_bytes,
+                    (hipStream_t)stream);
+}
+
+int coot_retrieval_row_norms_h(const void* rows, int dtype, int N, int d, float* norms, coot_stream_t stream) {
+  COOT_REQUIRE(dtype == COOT_GALLERY_BF16 || dtype == COOT_GALLERY_F16, "retrieval_row_norms_h: dtype = %d (COOT_GALLERY_BF16 or COOT_GALLERY_F16)", dtype);
+  COOT_REQUIRE(rows && norms, "retrieval_row_norms_h: null pointer");
+  COOT_REQUIRE(N >= 1 && d >= 1, "retrieval_row_norms_h: N = %d, d = %d", N, d);
+  const dim3 grid((N + 3) / 4);
+  if (dtype == COOT_GALLERY_BF16)
+    hipLaunchKernelGGL(rt_norms_kernel<unsigned short>, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned short*)rows, N,
+                       (const unsigned short*)nullptr, 0, d, norms, (float*)nullptr);
+  else
+    hipLaunchKernelGGL(rt_norms_kernel<_Float16>, grid, dim3(256), 0, (hipStream_t)stream, (const _Float16*)rows, N, (const _Float16*)nullptr, 0, d,
+                       norms, (float*)nullptr);
+  COOT_CHECK_LAUNCH("rt_norms_h");
   return 0;
+}
+
+int coot_retrieval_topk_few_h(const float* queries, const void* gallery, int gallery_dtype, const float* gallery_norms, int M, int N, int d, int K,
+                              int32_t* idx_out, float* score_out, float* sim_out, void* workspace, size_t workspace_bytes, coot_stream_t stream) {
+  COOT_REQUIRE(gallery_dtype == COOT_GALLERY_BF16 || gallery_dtype == COOT_GALLERY_F16,
+               "retrieval_topk_few_h: gallery_dtype = %d (COOT_GALLERY_BF16 or COOT_GALLERY_F16)", gallery_dtype);
+  if (gallery_dtype == COOT_GALLERY_BF16)
+    return few_search("retrieval_topk_few_h", queries, (const unsigned short*)gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, workspace,
+                      workspace_bytes, (hipStream_t)stream);
+  return few_search("retrieval_topk_few_h", queries, (const _Float16*)gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, workspace,
+                    workspace_bytes, (hipStream_t)stream);
 }
 
 size_t coot_retrieval_ranks_labeled_workspace_bytes(int M, int N, int d) {
@@ -1039,7 +1170,7 @@ int coot_retrieval_ranks_labeled(const float* queries, const float* gallery, con
   const int* lab = (const int*)labels;
   if (int rc = check_hip(hipMemsetAsync(w.best, 0, w.zero_bytes, st), "memset best, hist")) return rc;
   if (normalize) {
-    hipLaunchKernelGGL(rt_norms_kernel, dim3((M + N + 3) / 4), dim3(256), 0, st, queries, M, gallery, N, d, w.na, w.nb);
+    hipLaunchKernelGGL(rt_norms_kernel<float>, dim3((M + N + 3) / 4), dim3(256), 0, st, queries, M, gallery, N, d, w.na, w.nb);
     COOT_CHECK_LAUNCH("rt_norms");
     hipLaunchKernelGGL(rt_lab_own_kernel<true>, dim3(mt), dim3(256), 0, st, queries, gallery, lab, (const float*)w.na, (const float*)w.nb, M, N, d,
                        w.own, w.best);

@@ -9,7 +9,8 @@ in four launches, the N x N matrix is never materialised).  No CPU 
 compute_retrieval_topk / retrieval_topk_device: WHICH gallery items a query retrieves (the reference returns top1 only), for M
 queries against N gallery rows, M and N independent: the host mirror on a similarity matrix, and coot_retrieval_topk on the
 device (similarities and selection fused, no M x N matrix).  GalleryIndex: the same search for a few queries at a time on a
-gallery that stays on the device, its row norms computed once (coot_retrieval_topk_few: the same bytes, one sweep of the gallery).
+gallery that stays on the device, its row norms computed once (coot_retrieval_topk_few: the same bytes, one sweep of the gallery);
+the gallery may be held in bfloat16 or float16 (coot_retrieval_topk_few_h: the bytes of the search on the gallery widened to fp32).
 
 Sharded validation (data-parallel runs): retrieval_ranks_part_device counts one strip of rows, an integer all-reduce of the
 strips is the whole (compute_retrieval_device(dp=...)), retrieval_metrics_device turns rank vectors into the metrics;
@@ -106,36 +107,64 @@ def retrieval_topk_device(queries, gallery, k: int, normalize: bool = False, wan
 
 
 RETRIEVAL_FEW_MAX = 16  # include/coot_hip.h: COOT_RETRIEVAL_FEW_MAX
+GALLERY_BF16, GALLERY_F16 = 1, 2  # include/coot_hip.h: COOT_GALLERY_BF16, COOT_GALLERY_F16
+_STORAGE_NAMES = "torch.float32, torch.bfloat16 or torch.float16"
 
 
 class GalleryIndex:
     """A gallery that stays on the device between searches: a few queries at a time against a corpus that does not change.
 
-    GalleryIndex(gallery, normalize=True): gallery is a cuda float32 [N, d] tensor, kept by reference when contiguous (a copy
-    otherwise).  normalize=True computes the row norms once (coot_retrieval_row_norms) and every search divides by them, as
-    retrieval_topk_device(normalize=True) does.  The index does not watch the tensor: a caller that changes the gallery builds a
-    new index, or searches with stale norms.
+    GalleryIndex(gallery, normalize=True, storage=None): gallery is a cuda float32, bfloat16 or float16 [N, d] tensor.
+    storage=None keeps the tensor's own dtype, by reference when contiguous (a copy otherwise).  storage=torch.bfloat16 or
+    torch.float16 on a float32 gallery converts it once (gallery.to(storage): round to nearest even) and the float32 tensor is not
+    kept: half the bytes resident, half the bytes every search reads.  storage=torch.float32 on a 16-bit tensor widens it.  Any other
+    dtype or storage is a ValueError.  float16 overflows above 65 504: rows with larger entries become infinities, as .to() makes
+    them, and nothing checks for it on the device, so rows that are not normalised are better kept in bfloat16.  index.storage is
+    the dtype held, index.nbytes the bytes of the gallery and its norms.
+    normalize=True computes the row norms once (coot_retrieval_row_norms, coot_retrieval_row_norms_h) and every search divides by
+    them, as retrieval_topk_device(normalize=True) does.  The index does not watch the tensor: a caller that changes the gallery
+    builds a new index, or searches with stale norms.
 
     search(queries, k, want_sim=False) returns (idx int32 [M, k], scores float32 [M, k], sim [M, N] or None) on the device, no
-    synchronisation: the bytes of retrieval_topk_device(queries, gallery, k, normalize=...).  M <= RETRIEVAL_FEW_MAX goes through
-    coot_retrieval_topk_few with the stored norms: one sweep of the gallery, one row per thread.  M > RETRIEVAL_FEW_MAX goes through
-    retrieval_topk_device unchanged, which recomputes the gallery norms on every call.  queries [d] is one query.
-    1 <= k <= min(N, 128)."""
+    synchronisation: the bytes of retrieval_topk_device(queries, gallery, k, normalize=...), where gallery is the stored one widened
+    to float32 — a 16-bit value widens exactly, so only the storage differs, not the arithmetic or the order.  queries are float32;
+    queries [d] is one query.  1 <= k <= min(N, 128).
+    M <= RETRIEVAL_FEW_MAX goes through coot_retrieval_topk_few (coot_retrieval_topk_few_h on 16-bit storage) with the stored norms:
+    one sweep of the gallery, one row per thread.  M > RETRIEVAL_FEW_MAX on a float32 index goes through retrieval_topk_device
+    unchanged, which recomputes the gallery norms on every call; on a 16-bit index it goes through the few-query call in slices of
+    16 queries (a query's result does not depend on its batch-mates, and no float32 copy of the gallery is made): ceil(M / 16) sweeps
+    of the gallery, so large query batches are not what 16-bit storage is for."""
 
-    def __init__(self, gallery, normalize: bool = True):
+    def __init__(self, gallery, normalize: bool = True, storage=None):
         import torch
         from . import lib as _lib
+        codes = {torch.float32: 0, torch.bfloat16: GALLERY_BF16, torch.float16: GALLERY_F16}
+        if gallery.dtype not in codes:  # (before the device check: the message a caller needs first)
+            raise ValueError(f"GalleryIndex: a gallery of dtype {gallery.dtype}; it has to be {_STORAGE_NAMES}")
+        if storage is not None and storage not in codes:
+            raise ValueError(f"GalleryIndex: storage = {storage}; it has to be {_STORAGE_NAMES} (or None: the gallery's own dtype)")
         if not gallery.is_cuda:
             raise RuntimeError("GalleryIndex needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk)")
-        assert gallery.dtype == torch.float32 and gallery.dim() == 2 and gallery.shape[0] >= 1 and gallery.shape[1] >= 1, (gallery.dtype, gallery.shape)
-        self.gallery = gallery.contiguous()
+        assert gallery.dim() == 2 and gallery.shape[0] >= 1 and gallery.shape[1] >= 1, gallery.shape
+        self.storage = gallery.dtype if storage is None else storage
+        self.gallery = gallery.to(self.storage).contiguous()  # (.to() returns the tensor itself when the dtype is its own)
+        self._code = codes[self.storage]
         self.normalize = bool(normalize)
         self.norms = None
         if self.normalize:
             n, d = self.gallery.shape
             self.norms = torch.empty(n, dtype=torch.float32, device=gallery.device)
-            _lib.check(_lib.load().coot_retrieval_row_norms(self.gallery.data_ptr(), n, d, self.norms.data_ptr(),
-                                                            torch.cuda.current_stream().cuda_stream), "coot_retrieval_row_norms")
+            st = torch.cuda.current_stream().cuda_stream
+            if self._code:
+                _lib.check(_lib.load().coot_retrieval_row_norms_h(self.gallery.data_ptr(), self._code, n, d, self.norms.data_ptr(), st),
+                           "coot_retrieval_row_norms_h")
+            else:
+                _lib.check(_lib.load().coot_retrieval_row_norms(self.gallery.data_ptr(), n, d, self.norms.data_ptr(), st), "coot_retrieval_row_norms")
+
+    @property
+    def nbytes(self) -> int:
+        """The bytes the index keeps on the device: the gallery in its storage type and, when normalising, its fp32 row norms."""
+        return self.gallery.numel() * self.gallery.element_size() + (self.norms.numel() * 4 if self.norms is not None else 0)
 
     def search(self, queries, k: int, want_sim: bool = False):
         import torch
@@ -151,18 +180,26 @@ class GalleryIndex:
         if not 1 <= k <= min(n, 128):
             raise ValueError(f"GalleryIndex.search: k = {k} is outside 1 .. min(N = {n}, 128)")
         m = queries.shape[0]
-        if m > RETRIEVAL_FEW_MAX:
+        if m > RETRIEVAL_FEW_MAX and not self._code:
             return retrieval_topk_device(queries, self.gallery, k, normalize=self.normalize, want_sim=want_sim)
         queries = queries.contiguous()
         lib = _lib.load()
         dev = queries.device
-        ws = torch.empty(lib.coot_retrieval_topk_few_workspace_bytes(m, n, d, k), dtype=torch.uint8, device=dev)
+        ws = torch.empty(lib.coot_retrieval_topk_few_workspace_bytes(min(m, RETRIEVAL_FEW_MAX), n, d, k), dtype=torch.uint8, device=dev)
         idx = torch.empty(m, k, dtype=torch.int32, device=dev)
         scores = torch.empty(m, k, dtype=torch.float32, device=dev)
         sim = torch.empty(m, n, dtype=torch.float32, device=dev) if want_sim else None
-        _lib.check(lib.coot_retrieval_topk_few(queries.data_ptr(), self.gallery.data_ptr(), self.norms.data_ptr() if self.normalize else None,
-                                               m, n, d, k, idx.data_ptr(), scores.data_ptr(), sim.data_ptr() if want_sim else None,
-                                               ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream), "coot_retrieval_topk_few")
+        norms = self.norms.data_ptr() if self.normalize else None
+        st = torch.cuda.current_stream().cuda_stream
+        if not self._code:
+            _lib.check(lib.coot_retrieval_topk_few(queries.data_ptr(), self.gallery.data_ptr(), norms, m, n, d, k, idx.data_ptr(), scores.data_ptr(),
+                                                   sim.data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(), st), "coot_retrieval_topk_few")
+            return idx, scores, sim
+        for i in range(0, m, RETRIEVAL_FEW_MAX):  # one slice unless M > RETRIEVAL_FEW_MAX; the calls of a stream run in order: one workspace
+            mm = min(RETRIEVAL_FEW_MAX, m - i)
+            _lib.check(lib.coot_retrieval_topk_few_h(queries[i:].data_ptr(), self.gallery.data_ptr(), self._code, norms, mm, n, d, k,
+                                                     idx[i:].data_ptr(), scores[i:].data_ptr(), sim[i:].data_ptr() if want_sim else None,
+                                                     ws.data_ptr(), ws.numel(), st), "coot_retrieval_topk_few_h")
         return idx, scores, sim
 
 

@@ -381,6 +381,23 @@ int coot_retrieval_topk_few(const float* queries, const float* gallery, const fl
                             int32_t* idx_out, float* score_out, float* sim_out, void* workspace, size_t workspace_bytes,
                             coot_stream_t stream);
 
+/* ---- the prepared gallery stored in 16-bit floats ---------------------------------------------------------------------
+ * Only the storage changes: a bfloat16 or IEEE-half value widens to fp32 exactly, and the arithmetic and the total order are those
+ * above.  dtype / gallery_dtype: COOT_GALLERY_BF16 or COOT_GALLERY_F16, the element type of the [N, d] rows (2-byte aligned, row
+ * stride d), independent of the library's MFMA operand format: both builds serve both.
+ * coot_retrieval_row_norms_h: norms[j] = the bytes coot_retrieval_row_norms writes for the rows widened to fp32.
+ * coot_retrieval_topk_few_h: idx_out, score_out and the optional sim_out are byte for byte the results of coot_retrieval_topk_few on
+ * the gallery widened to fp32, with the same queries (fp32), gallery_norms (NULL: rows used as they are), M, K, workspace
+ * (coot_retrieval_topk_few_workspace_bytes: it does not depend on the gallery's type) and split option; no widened copy is made:
+ * the sweep reads the 16-bit rows (half the bytes) and widens at staging.  Neither call retains a pointer.  A refused call
+ * (unknown dtype, null pointer, M or K outside its range, workspace too small) writes nothing.  No allocation, no synchronisation. */
+#define COOT_GALLERY_BF16 1
+#define COOT_GALLERY_F16 2
+int coot_retrieval_row_norms_h(const void* rows, int dtype, int N, int d, float* norms, coot_stream_t stream);
+int coot_retrieval_topk_few_h(const float* queries, const void* gallery, int gallery_dtype, const float* gallery_norms, int M, int N,
+                              int d, int K, int32_t* idx_out, float* score_out, float* sim_out, void* workspace, size_t workspace_bytes,
+                              coot_stream_t stream);
+
 /* ---- labelled retrieval ranking on the device: M queries, N gallery rows, several queries per row -----------------------
  * coot_retrieval_ranks without the assumption "N x N, ground truth on the diagonal": labels[i] (device int32 [M]) is the gallery
  * row of query i.  Several queries may share a row (a second annotation set, several captions per clip), rows may have no query
