@@ -316,11 +316,20 @@ struct TkFold {
 
 size_t tk_lds_bytes(int K) { return (size_t)2 * RT * RP * 4 + (size_t)RT * RT * 8 + (size_t)RT * K * 8 + 2 * RT * 4; }
 
+// The result of an unfilled slot in the masked searches (fewer than K kept rows): index -1, score -inf.  Word 0 is a real entry
+// only for the all-ones NaN at column 0 (tk_pack), which a masked search therefore reports as unfilled.
+__device__ __forceinline__ int tk_idx_masked(tk_entry_t e) { return e ? (int)(unsigned)e : -1; }
+__device__ __forceinline__ float tk_score_masked(tk_entry_t e) { return e ? tk_score(e) : __uint_as_float(0xFF800000u); }
+
 // grid (S, row tiles); LDS: As | Bs | cand [RT][RT] | list [RT][K] | cnt [RT] | ncand [RT]   (tk_lds_bytes)
-template <bool NORM>
+// MASKED (coot_retrieval_topk_masked): keep [N] bytes, nonzero = the gallery row may be returned.  A row whose byte is zero is
+// never a candidate (its accumulator is neither compared nor appended); sim still holds every similarity.  Without sim a column
+// tile that keeps no row is skipped before its first load: the vote is a workgroup reduction, so every thread takes the same
+// way round the barriers.  keep is the last parameter: the unmasked instantiations read the arguments they always read.
+template <bool NORM, bool MASKED>
 __global__ __launch_bounds__(256) void rt_topk_kernel(const float* A, const float* B, const float* nA, const float* nB, int M, int N, int d,
                                                       int K, int tiles_per_split, int S, float* sim, tk_entry_t* part, int* idx_out,
-                                                      float* score_out) {
+                                                      float* score_out, const unsigned char* keep) {
   extern __shared__ __attribute__((aligned(16))) char tk_lds[];
   float (*As)[RP] = (float (*)[RP])tk_lds;
   float (*Bs)[RP] = (float (*)[RP])(tk_lds + RT * RP * 4);
@@ -335,6 +344,12 @@ __global__ __launch_bounds__(256) void rt_topk_kernel(const float* A, const floa
   for (int e = tid; e < RT * K; e += 256) list[e] = 0ull;  // 0 = behind every entry: an unfilled slot
   for (int tj = t0; tj < t1; ++tj) {
     const int j0 = tj * RT;
+    unsigned kp = 0u;  // MASKED: bit c = the keep flag of column j0 + 4 tx + c
+    if constexpr (MASKED) {
+      if (!sim && !__syncthreads_or(tid < RT && j0 + tid < N && keep[j0 + tid])) continue;  // (uniform: nothing of this tile is touched)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) kp |= (j0 + 4 * tx + c < N && keep[j0 + 4 * tx + c]) ? 1u << c : 0u;
+    }
     Tile t;
     tile_dot<NORM>(A, B, M, N, d, i0, j0, As, Bs, t, nA, nB);  // ends with a barrier: lists and counters of the previous tile are settled
 #pragma unroll
@@ -349,6 +364,7 @@ __global__ __launch_bounds__(256) void rt_topk_kernel(const float* A, const floa
         if (j >= N) continue;
         const float s = t.acc[r][c];
         if (sim) sim[(long)i * N + j] = s;
+        if constexpr (MASKED) { if (!(kp >> c & 1u)) continue; }
         const tk_entry_t e = tk_pack(s, j);
         if (!full || e > kth) cand[row * RT + atomicAdd(&ncand[row], 1)] = e;  // <= RT columns of this tile per row
       }
@@ -374,8 +390,8 @@ __global__ __launch_bounds__(256) void rt_topk_kernel(const float* A, const floa
     if (i >= M) continue;
     const tk_entry_t v = list[e];
     if (S == 1) {
-      idx_out[(long)i * K + r] = (int)(unsigned)v;
-      score_out[(long)i * K + r] = tk_score(v);
+      idx_out[(long)i * K + r] = MASKED ? tk_idx_masked(v) : (int)(unsigned)v;
+      score_out[(long)i * K + r] = MASKED ? tk_score_masked(v) : tk_score(v);
     } else {
       part[((long)i * S + blockIdx.x) * K + r] = v;
     }
@@ -383,6 +399,12 @@ __global__ __launch_bounds__(256) void rt_topk_kernel(const float* A, const floa
 }
 
 // one wave per row: part [M][S][K], every list sorted best first, unfilled slots 0 at its end
+// MASKED: the real entries of a row may total R < K (a split whose columns are all masked hands in an all-unfilled list).  A real
+// entry's rank is its position among the real ones, below R.  An unfilled slot at position p of list s, which holds n_s real
+// entries, has every real entry of the other lists ahead of it: rank p + (R - n_s) >= R, and as p runs over [n_s, K) that covers
+// [R, K + R - n_s), which contains [R, K) whichever list it is.  So every output slot is written; unfilled slots of different lists
+// may share a rank, and all of them write (-1, -inf).
+template <bool MASKED>
 __global__ __launch_bounds__(256) void rt_topk_merge_kernel(const tk_entry_t* part, int M, int S, int K, int* idx_out, float* score_out) {
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
@@ -393,9 +415,9 @@ __global__ __launch_bounds__(256) void rt_topk_merge_kernel(const tk_entry_t* pa
     int rank = e - s * K;
     for (int t = 0; t < S && rank < K; ++t)
       if (t != s) rank += tk_ahead(P + t * K, K, v);
-    if (rank < K) {  // (an unfilled slot is behind all N >= K real entries)
-      idx_out[(long)row * K + rank] = (int)(unsigned)v;
-      score_out[(long)row * K + rank] = tk_score(v);
+    if (rank < K) {  // (unmasked: an unfilled slot is behind all N >= K real entries)
+      idx_out[(long)row * K + rank] = MASKED ? tk_idx_masked(v) : (int)(unsigned)v;
+      score_out[(long)row * K + rank] = MASKED ? tk_score_masked(v) : tk_score(v);
     }
   }
 }
@@ -499,10 +521,13 @@ __device__ __forceinline__ void few_fma_chunk(const float* tile, const float* qs
 
 // grid (S); MQ = M rounded up to 1, 2, 4, 8, 16 accumulators; LDS: tile [FR][RP] | qs [RK][16] | list [MQ][K] | cnt | ncand
 // GT: the gallery's element type, float, unsigned short (bfloat16) or _Float16
-template <typename GT, int MQ, bool NORM>
+// MASKED (coot_retrieval_topk_few_masked): keep [N] as in rt_topk_kernel, one byte per thread.  Without sim a 128-row block that
+// keeps no row is skipped before its first load (no gallery bytes, no FMAs, no fold); the vote is a workgroup reduction.
+template <typename GT, int MQ, bool NORM, bool MASKED>
 __global__ __launch_bounds__(FR) void rt_few_kernel(const GT* __restrict__ G, const float* __restrict__ gnorm, const float* __restrict__ qn, int M,
                                                     int N, int d, int K, int blocks_per_split, int S, int vec, float* __restrict__ sim,
-                                                    tk_entry_t* __restrict__ part, int* __restrict__ idx_out, float* __restrict__ score_out) {
+                                                    tk_entry_t* __restrict__ part, int* __restrict__ idx_out, float* __restrict__ score_out,
+                                                    const unsigned char* __restrict__ keep) {
   extern __shared__ __attribute__((aligned(16))) char few_lds[];
   float* tile = (float*)few_lds;
   float* qs = tile + FR * RP;
@@ -517,6 +542,11 @@ __global__ __launch_bounds__(FR) void rt_few_kernel(const GT* __restrict__ G, co
   for (int e = tid; e < MQ * K; e += FR) list[e] = 0ull;  // 0 = behind every entry: an unfilled slot
   for (int b = b0; b < b1; ++b) {
     const int j0 = b * FR;
+    bool kept = true;  // MASKED: the keep flag of this thread's row j0 + tid
+    if constexpr (MASKED) {
+      kept = j0 + tid < N && keep[j0 + tid];
+      if (!sim && !__syncthreads_or(kept)) continue;  // (uniform: nothing of this block is touched)
+    }
     float acc[MQ];
     if constexpr (sizeof(GT) == 4) {
       const int sr = tid >> 3, sk = (tid & 7) * 4;  // staging: floats sk .. sk + 3 of the rows sr + 16 q of a chunk
@@ -638,6 +668,7 @@ __global__ __launch_bounds__(FR) void rt_few_kernel(const GT* __restrict__ G, co
         if (i < M) {
           const float s = acc[i];
           if (sim) sim[(long)i * N + j] = s;
+          if constexpr (MASKED) { if (!kept) continue; }
           const tk_entry_t e = tk_pack(s, j);
           if (cnt[i] < K || e > list[i * K + K - 1]) cand[i * FR + atomicAdd(&ncand[i], 1)] = e;  // <= FR rows of this block per query
         }
@@ -671,8 +702,8 @@ __global__ __launch_bounds__(FR) void rt_few_kernel(const GT* __restrict__ G, co
     const int i = e / K, r = e - i * K;
     const tk_entry_t v = list[e];
     if (S == 1) {
-      idx_out[e] = (int)(unsigned)v;
-      score_out[e] = tk_score(v);
+      idx_out[e] = MASKED ? tk_idx_masked(v) : (int)(unsigned)v;
+      score_out[e] = MASKED ? tk_score_masked(v) : tk_score(v);
     } else {
       part[((long)i * S + blockIdx.x) * K + r] = v;
     }
@@ -680,7 +711,9 @@ __global__ __launch_bounds__(FR) void rt_few_kernel(const GT* __restrict__ G, co
 }
 
 // grid (groups, M): the lists [g FEW_G, g FEW_G + ns) of in [M][S][K] -> list g of out [M][S_out][K], or (FINAL, one group) idx / score
-template <bool FINAL>
+// Short and empty lists (MASKED: fewer than K kept rows in a split, or none): rt_topk_merge_kernel's argument holds for every
+// group and every round, so all K slots of a merged list are written, the unfilled ones with 0, or (FINAL, MASKED) (-1, -inf).
+template <bool FINAL, bool MASKED>
 __global__ __launch_bounds__(FEW_MT) void rt_few_merge_kernel(const tk_entry_t* in, int S, int K, tk_entry_t* out, int S_out, int* idx_out,
                                                            float* score_out) {
   extern __shared__ __attribute__((aligned(16))) char few_lds[];
@@ -697,9 +730,9 @@ __global__ __launch_bounds__(FEW_MT) void rt_few_merge_kernel(const tk_entry_t* 
     for (int t = 0; t < ns && rank < K; ++t)
       if (t != s) rank += tk_ahead(P + t * K, K, v);
     if (rank < K) {
-      if (FINAL) {  // (an unfilled slot is behind all N >= K real entries)
-        idx_out[(long)q * K + rank] = (int)(unsigned)v;
-        score_out[(long)q * K + rank] = tk_score(v);
+      if (FINAL) {  // (unmasked: an unfilled slot is behind all N >= K real entries)
+        idx_out[(long)q * K + rank] = MASKED ? tk_idx_masked(v) : (int)(unsigned)v;
+        score_out[(long)q * K + rank] = MASKED ? tk_score_masked(v) : tk_score(v);
       } else {
         out[((long)q * S_out + g) * K + rank] = v;
       }
@@ -732,23 +765,35 @@ FewWs few_layout(void* base, int M, int d, int K, int cap) {
   return w;
 }
 
-template <typename GT, int MQ>
-void few_launch(const FewPlan& p, const FewWs& w, const GT* gallery, const float* gallery_norms, int M, int N, int d, int K, int32_t* idx_out,
-                float* score_out, float* sim_out, hipStream_t st) {
+template <typename GT, int MQ, bool MASKED>
+void few_launch(const FewPlan& p, const FewWs& w, const GT* gallery, const float* gallery_norms, const unsigned char* keep, int M, int N, int d, int K,
+                int32_t* idx_out, float* score_out, float* sim_out, hipStream_t st) {
   const int vec = d % (16 / (int)sizeof(GT)) == 0 && ((uintptr_t)gallery & 15) == 0;  // every row starts 16-byte aligned
   const size_t lds = few_lds_bytes(MQ, K);
   if (gallery_norms)
-    hipLaunchKernelGGL((rt_few_kernel<GT, MQ, true>), dim3(p.S), dim3(FR), lds, st, gallery, gallery_norms, (const float*)w.qn, M, N, d, K, p.blocks, p.S,
-                       vec, sim_out, w.part_a, (int*)idx_out, score_out);
+    hipLaunchKernelGGL((rt_few_kernel<GT, MQ, true, MASKED>), dim3(p.S), dim3(FR), lds, st, gallery, gallery_norms, (const float*)w.qn, M, N, d, K,
+                       p.blocks, p.S, vec, sim_out, w.part_a, (int*)idx_out, score_out, keep);
   else
-    hipLaunchKernelGGL((rt_few_kernel<GT, MQ, false>), dim3(p.S), dim3(FR), lds, st, gallery, (const float*)nullptr, (const float*)w.qn, M, N, d, K,
-                       p.blocks, p.S, vec, sim_out, w.part_a, (int*)idx_out, score_out);
+    hipLaunchKernelGGL((rt_few_kernel<GT, MQ, false, MASKED>), dim3(p.S), dim3(FR), lds, st, gallery, (const float*)nullptr, (const float*)w.qn, M, N, d,
+                       K, p.blocks, p.S, vec, sim_out, w.part_a, (int*)idx_out, score_out, keep);
+}
+template <typename GT, bool MASKED>
+void few_launch_mq(const FewPlan& p, const FewWs& w, const GT* gallery, const float* gallery_norms, const unsigned char* keep, int M, int N, int d, int K,
+                   int32_t* idx_out, float* score_out, float* sim_out, hipStream_t st) {
+  switch (p.MQ) {
+    case 1: few_launch<GT, 1, MASKED>(p, w, gallery, gallery_norms, keep, M, N, d, K, idx_out, score_out, sim_out, st); break;
+    case 2: few_launch<GT, 2, MASKED>(p, w, gallery, gallery_norms, keep, M, N, d, K, idx_out, score_out, sim_out, st); break;
+    case 4: few_launch<GT, 4, MASKED>(p, w, gallery, gallery_norms, keep, M, N, d, K, idx_out, score_out, sim_out, st); break;
+    case 8: few_launch<GT, 8, MASKED>(p, w, gallery, gallery_norms, keep, M, N, d, K, idx_out, score_out, sim_out, st); break;
+    default: few_launch<GT, 16, MASKED>(p, w, gallery, gallery_norms, keep, M, N, d, K, idx_out, score_out, sim_out, st); break;
+  }
 }
 
-// coot_retrieval_topk_few (GT = float) and coot_retrieval_topk_few_h (a 16-bit GT): fn names the entry in a refusal
+// coot_retrieval_topk_few (GT = float), coot_retrieval_topk_few_h (a 16-bit GT) and coot_retrieval_topk_few_masked (any GT; keep
+// == nullptr: the unmasked kernels, launched as the other two launch them): fn names the entry in a refusal
 template <typename GT>
-int few_search(const char* fn, const float* queries, const GT* gallery, const float* gallery_norms, int M, int N, int d, int K, int32_t* idx_out,
-               float* score_out, float* sim_out, void* workspace, size_t workspace_bytes, hipStream_t st) {
+int few_search(const char* fn, const float* queries, const GT* gallery, const float* gallery_norms, const unsigned char* keep, int M, int N, int d, int K,
+               int32_t* idx_out, float* score_out, float* sim_out, void* workspace, size_t workspace_bytes, hipStream_t st) {
   COOT_REQUIRE(queries && gallery && idx_out && score_out && workspace, "%s: null pointer", fn);
   COOT_REQUIRE(M >= 1 && M <= FEW_MAX && N >= 1 && d >= 1, "%s: M = %d (1 .. %d), N = %d, d = %d", fn, M, FEW_MAX, N, d);
   COOT_REQUIRE(K >= 1 && K <= N && K <= TK_MAX, "%s: K = %d is outside 1 .. min(N = %d, %d)", fn, K, N, TK_MAX);
@@ -758,13 +803,8 @@ int few_search(const char* fn, const float* queries, const GT* gallery, const fl
   COOT_REQUIRE(w.bytes <= workspace_bytes, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, w.bytes);
   hipLaunchKernelGGL(rt_few_prep_kernel, dim3(FEW_MAX), dim3(64), 0, st, queries, M, d, (d + RK - 1) / RK * RK, gallery_norms != nullptr, w.qnorm, w.qn);
   COOT_CHECK_LAUNCH("rt_few_prep");
-  switch (p.MQ) {
-    case 1: few_launch<GT, 1>(p, w, gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, st); break;
-    case 2: few_launch<GT, 2>(p, w, gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, st); break;
-    case 4: few_launch<GT, 4>(p, w, gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, st); break;
-    case 8: few_launch<GT, 8>(p, w, gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, st); break;
-    default: few_launch<GT, 16>(p, w, gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, st); break;
-  }
+  if (keep) few_launch_mq<GT, true>(p, w, gallery, gallery_norms, keep, M, N, d, K, idx_out, score_out, sim_out, st);
+  else few_launch_mq<GT, false>(p, w, gallery, gallery_norms, keep, M, N, d, K, idx_out, score_out, sim_out, st);
   COOT_CHECK_LAUNCH("rt_few");
   if (p.S == 1) return 0;
   // merge by rank in rounds of <= FEW_G lists, the two list buffers taking turns
@@ -773,11 +813,16 @@ int few_search(const char* fn, const float* queries, const GT* gallery, const fl
   int S = p.S;
   while (S > FEW_G) {
     const int So = (S + FEW_G - 1) / FEW_G;
-    hipLaunchKernelGGL(rt_few_merge_kernel<false>, dim3(So, M), dim3(FEW_MT), (size_t)FEW_G * K * 8, st, cur, S, K, nxt, So, (int*)nullptr, (float*)nullptr);
+    hipLaunchKernelGGL((rt_few_merge_kernel<false, false>), dim3(So, M), dim3(FEW_MT), (size_t)FEW_G * K * 8, st, cur, S, K, nxt, So, (int*)nullptr, (float*)nullptr);
     COOT_CHECK_LAUNCH("rt_few_merge");
     tk_entry_t* done = nxt; nxt = (tk_entry_t*)cur; cur = done; S = So;
   }
-  hipLaunchKernelGGL(rt_few_merge_kernel<true>, dim3(1, M), dim3(FEW_MT), (size_t)S * K * 8, st, cur, S, K, (tk_entry_t*)nullptr, 1, (int*)idx_out, score_out);
+  if (keep)
+    hipLaunchKernelGGL((rt_few_merge_kernel<true, true>), dim3(1, M), dim3(FEW_MT), (size_t)S * K * 8, st, cur, S, K, (tk_entry_t*)nullptr, 1, (int*)idx_out,
+                       score_out);
+  else
+    hipLaunchKernelGGL((rt_few_merge_kernel<true, false>), dim3(1, M), dim3(FEW_MT), (size_t)S * K * 8, st, cur, S, K, (tk_entry_t*)nullptr, 1, (int*)idx_out,
+                       score_out);
   COOT_CHECK_LAUNCH("rt_few_merge");
   return 0;
 }
@@ -998,6 +1043,45 @@ LabWs lab_layout(void* base, int M, int N) {
   return w;
 }
 
+// coot_retrieval_topk and coot_retrieval_topk_masked (keep == nullptr: the unmasked kernels, launched as coot_retrieval_topk
+// launches them): fn names the entry in a refusal
+template <bool MASKED>
+void topk_launch(const TkSplit& sp, const TkWs& w, const float* queries, const float* gallery, const unsigned char* keep, int M, int N, int d, int K,
+                 int normalize, int32_t* idx_out, float* score_out, float* sim_out, hipStream_t st) {
+  const dim3 grid(sp.S, (M + RT - 1) / RT);
+  const size_t lds = tk_lds_bytes(K);
+  if (normalize)
+    hipLaunchKernelGGL((rt_topk_kernel<true, MASKED>), grid, dim3(256), lds, st, queries, gallery, (const float*)w.na, (const float*)w.nb, M, N, d, K,
+                       sp.tiles, sp.S, sim_out, w.part, (int*)idx_out, score_out, keep);
+  else
+    hipLaunchKernelGGL((rt_topk_kernel<false, MASKED>), grid, dim3(256), lds, st, queries, gallery, (const float*)nullptr, (const float*)nullptr, M, N, d,
+                       K, sp.tiles, sp.S, sim_out, w.part, (int*)idx_out, score_out, keep);
+}
+int topk_search(const char* fn, const float* queries, const float* gallery, const unsigned char* keep, int M, int N, int d, int K, int normalize,
+                int32_t* idx_out, float* score_out, float* sim_out, void* workspace, size_t workspace_bytes, hipStream_t st) {
+  COOT_REQUIRE(queries && gallery && idx_out && score_out && workspace, "%s: null pointer", fn);
+  COOT_REQUIRE(M >= 1 && N >= 1 && d >= 1 && (M + RT - 1) / RT <= 65535, "%s: M = %d, N = %d, d = %d", fn, M, N, d);
+  COOT_REQUIRE(K >= 1 && K <= N && K <= TK_MAX, "%s: K = %d is outside 1 .. min(N = %d, %d)", fn, K, N, TK_MAX);
+  const TkSplit sp = tk_split(M, N);
+  TkWs w = tk_layout(workspace, M, N, K, sp.S);
+  COOT_REQUIRE(w.bytes <= workspace_bytes, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, w.bytes);
+  if (normalize) {
+    hipLaunchKernelGGL(rt_norms_kernel<float>, dim3((M + N + 3) / 4), dim3(256), 0, st, queries, M, gallery, N, d, w.na, w.nb);
+    COOT_CHECK_LAUNCH("rt_norms");
+  }
+  if (keep) topk_launch<true>(sp, w, queries, gallery, keep, M, N, d, K, normalize, idx_out, score_out, sim_out, st);
+  else topk_launch<false>(sp, w, queries, gallery, keep, M, N, d, K, normalize, idx_out, score_out, sim_out, st);
+  COOT_CHECK_LAUNCH("rt_topk");
+  if (sp.S > 1) {
+    if (keep)
+      hipLaunchKernelGGL(rt_topk_merge_kernel<true>, dim3((M + 3) / 4), dim3(256), 0, st, (const tk_entry_t*)w.part, M, sp.S, K, (int*)idx_out, score_out);
+    else
+      hipLaunchKernelGGL(rt_topk_merge_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, st, (const tk_entry_t*)w.part, M, sp.S, K, (int*)idx_out, score_out);
+    COOT_CHECK_LAUNCH("rt_topk_merge");
+  }
+  return 0;
+}
+
 }  // namespace
 void set_rt_topk_splits(int n) { g_rt_topk_splits = n; }
 int get_rt_topk_splits() { return g_rt_topk_splits; }
@@ -1080,30 +1164,14 @@ size_t coot_retrieval_topk_workspace_bytes(int M, int N, int d, int K) {
 
 int coot_retrieval_topk(const float* queries, const float* gallery, int M, int N, int d, int K, int normalize, int32_t* idx_out,
                         float* score_out, float* sim_out, void* workspace, size_t workspace_bytes, coot_stream_t stream) {
-  COOT_REQUIRE(queries && gallery && idx_out && score_out && workspace, "retrieval_topk: null pointer");
-  COOT_REQUIRE(M >= 1 && N >= 1 && d >= 1 && (M + RT - 1) / RT <= 65535, "retrieval_topk: M = %d, N = %d, d = %d", M, N, d);
-  COOT_REQUIRE(K >= 1 && K <= N && K <= TK_MAX, "retrieval_topk: K = %d is outside 1 .. min(N = %d, %d)", K, N, TK_MAX);
-  hipStream_t st = (hipStream_t)stream;
-  const TkSplit sp = tk_split(M, N);
-  TkWs w = tk_layout(workspace, M, N, K, sp.S);
-  COOT_REQUIRE(w.bytes <= workspace_bytes, "retrieval_topk: workspace too small (%zu < %zu)", workspace_bytes, w.bytes);
-  const dim3 grid(sp.S, (M + RT - 1) / RT);
-  const size_t lds = tk_lds_bytes(K);
-  if (normalize) {
-    hipLaunchKernelGGL(rt_norms_kernel<float>, dim3((M + N + 3) / 4), dim3(256), 0, st, queries, M, gallery, N, d, w.na, w.nb);
-    COOT_CHECK_LAUNCH("rt_norms");
-    hipLaunchKernelGGL(rt_topk_kernel<true>, grid, dim3(256), lds, st, queries, gallery, (const float*)w.na, (const float*)w.nb, M, N, d, K,
-                       sp.tiles, sp.S, sim_out, w.part, (int*)idx_out, score_out);
-  } else {
-    hipLaunchKernelGGL(rt_topk_kernel<false>, grid, dim3(256), lds, st, queries, gallery, (const float*)nullptr, (const float*)nullptr, M, N, d, K,
-                       sp.tiles, sp.S, sim_out, w.part, (int*)idx_out, score_out);
-  }
-  COOT_CHECK_LAUNCH("rt_topk");
-  if (sp.S > 1) {
-    hipLaunchKernelGGL(rt_topk_merge_kernel, dim3((M + 3) / 4), dim3(256), 0, st, (const tk_entry_t*)w.part, M, sp.S, K, (int*)idx_out, score_out);
-    COOT_CHECK_LAUNCH("rt_topk_merge");
-  }
-  return 0;
+  return topk_search("retrieval_topk", queries, gallery, nullptr, M, N, d, K, normalize, idx_out, score_out, sim_out, workspace, workspace_bytes,
+                     (hipStream_t)stream);
+}
+
+int coot_retrieval_topk_masked(const float* queries, const float* gallery, const uint8_t* keep, int M, int N, int d, int K, int normalize,
+                               int32_t* idx_out, float* score_out, float* sim_out, void* workspace, size_t workspace_bytes, coot_stream_t stream) {
+  return topk_search("retrieval_topk_masked", queries, gallery, keep, M, N, d, K, normalize, idx_out, score_out, sim_out, workspace, workspace_bytes,
+                     (hipStream_t)stream);
 }
 
 int coot_retrieval_row_norms(const float* rows, int N, int d, float* norms, coot_stream_t stream) {
@@ -1121,7 +1189,7 @@ size_t coot_retrieval_topk_few_workspace_bytes(int M, int N, int d, int K) {
 
 int coot_retrieval_topk_few(const float* queries, const float* gallery, const float* gallery_norms, int M, int N, int d, int K, int32_t* idx_out,
                             float* score_out, float* sim_out, void* workspace, size_t workspace_bytes, coot_stream_t stream) {
-  return few_search("retrieval_topk_few", queries, gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, workspace, workspace_bytes,
+  return few_search("retrieval_topk_few", queries, gallery, gallery_norms, nullptr, M, N, d, K, idx_out, score_out, sim_out, workspace, workspace_bytes,
                     (hipStream_t)stream);
 }
 
@@ -1145,10 +1213,25 @@ int coot_retrieval_topk_few_h(const float* queries, const void* gallery, int gal
   COOT_REQUIRE(gallery_dtype == COOT_GALLERY_BF16 || gallery_dtype == COOT_GALLERY_F16,
                "retrieval_topk_few_h: gallery_dtype = %d (COOT_GALLERY_BF16 or COOT_GALLERY_F16)", gallery_dtype);
   if (gallery_dtype == COOT_GALLERY_BF16)
-    return few_search("retrieval_topk_few_h", queries, (const unsigned short*)gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, workspace,
+    return few_search("retrieval_topk_few_h", queries, (const unsigned short*)gallery, gallery_norms, nullptr, M, N, d, K, idx_out, score_out, sim_out, workspace,
                       workspace_bytes, (hipStream_t)stream);
-  return few_search("retrieval_topk_few_h", queries, (const _Float16*)gallery, gallery_norms, M, N, d, K, idx_out, score_out, sim_out, workspace,
+  return few_search("retrieval_topk_few_h", queries, (const _Float16*)gallery, gallery_norms, nullptr, M, N, d, K, idx_out, score_out, sim_out, workspace,
                     workspace_bytes, (hipStream_t)stream);
+}
+
+int coot_retrieval_topk_few_masked(const float* queries, const void* gallery, int gallery_dtype, const float* gallery_norms, const uint8_t* keep, int M,
+                                   int N, int d, int K, int32_t* idx_out, float* score_out, float* sim_out, void* workspace, size_t workspace_bytes,
+                                   coot_stream_t stream) {
+  const char* fn = "retrieval_topk_few_masked";
+  COOT_REQUIRE(gallery_dtype == COOT_GALLERY_F32 || gallery_dtype == COOT_GALLERY_BF16 || gallery_dtype == COOT_GALLERY_F16,
+               "%s: gallery_dtype = %d (COOT_GALLERY_F32, COOT_GALLERY_BF16 or COOT_GALLERY_F16)", fn, gallery_dtype);
+  hipStream_t st = (hipStream_t)stream;
+  if (gallery_dtype == COOT_GALLERY_F32)
+    return few_search(fn, queries, (const float*)gallery, gallery_norms, keep, M, N, d, K, idx_out, score_out, sim_out, workspace, workspace_bytes, st);
+  if (gallery_dtype == COOT_GALLERY_BF16)
+    return few_search(fn, queries, (const unsigned short*)gallery, gallery_norms, keep, M, N, d, K, idx_out, score_out, sim_out, workspace,
+                      workspace_bytes, st);
+  return few_search(fn, queries, (const _Float16*)gallery, gallery_norms, keep, M, N, d, K, idx_out, score_out, sim_out, workspace, workspace_bytes, st);
 }
 
 size_t coot_retrieval_ranks_labeled_workspace_bytes(int M, int N, int d) {

@@ -11,6 +11,9 @@ queries against N gallery rows, M and N independent: the host mirror on a simila
 device (similarities and selection fused, no M x N matrix).  GalleryIndex: the same search for a few queries at a time on a
 gallery that stays on the device, its row norms computed once (coot_retrieval_topk_few: the same bytes, one sweep of the gallery);
 the gallery may be held in bfloat16 or float16 (coot_retrieval_topk_few_h: the bytes of the search on the gallery widened to fp32).
+Filtered search (compute_retrieval_topk_masked; keep= of retrieval_topk_device and GalleryIndex.search; GalleryIndex.remove /
+restore): a keep flag per gallery row that the selection consults (coot_retrieval_topk_masked, coot_retrieval_topk_few_masked) —
+the bytes of the unfiltered search on gallery[keep] with its indices mapped back, without the copy.
 
 Sharded validation (data-parallel runs): retrieval_ranks_part_device counts one strip of rows, an integer all-reduce of the
 strips is the whole (compute_retrieval_device(dp=...)), retrieval_metrics_device turns rank vectors into the metrics;
@@ -57,6 +60,38 @@ def compute_retrieval_topk(sim: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndar
     return idx.astype(np.int32), np.take_along_axis(sim, idx, axis=1)
 
 
+def compute_retrieval_topk_masked(sim: np.ndarray, k: int, keep) -> Tuple[np.ndarray, np.ndarray]:
+    """compute_retrieval_topk restricted to the columns with keep[j] != 0 (keep: [N] booleans or bytes): compute_retrieval_topk of
+    sim[:, keep] with its columns mapped back through np.nonzero(keep).  1 <= k <= N whatever the mask holds; with c < k kept
+    columns the slots r >= c of every row are idx = -1, score = -inf."""
+    sim = np.asarray(sim)
+    keep = np.asarray(keep)
+    assert sim.ndim == 2 and 1 <= k <= sim.shape[1] and keep.shape == (sim.shape[1],), (sim.shape, k, keep.shape)
+    cols = np.nonzero(keep)[0]
+    c = min(int(k), len(cols))
+    idx = np.full((sim.shape[0], k), -1, np.int32)
+    scores = np.full((sim.shape[0], k), -np.inf, sim.dtype)
+    if c:
+        sub_idx, sub_scores = compute_retrieval_topk(sim[:, cols], c)
+        idx[:, :c] = cols[sub_idx]
+        scores[:, :c] = sub_scores
+    return idx, scores
+
+
+def _check_keep(fn: str, keep, n: int):
+    """The keep argument of a filtered search, checked on the host before anything is launched: a torch.bool or torch.uint8 tensor
+    [N] (ValueError), on the device (RuntimeError naming the host mirror).  Returns it as contiguous bytes (a view where it can be)."""
+    import torch
+    if not isinstance(keep, torch.Tensor) or keep.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"{fn}: keep has to be a torch.bool or torch.uint8 tensor, not {getattr(keep, 'dtype', type(keep).__name__)}")
+    if tuple(keep.shape) != (n,):
+        raise ValueError(f"{fn}: keep of shape {tuple(keep.shape)}, a gallery of {n} rows (one flag per row: [{n}])")
+    if not keep.is_cuda:
+        raise RuntimeError(f"{fn} needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk_masked)")
+    keep = keep.contiguous()
+    return keep.view(torch.uint8) if keep.dtype is torch.bool else keep
+
+
 def _device_pair(fn: str, host: str, a, b, dtype, same_shape: bool = True, dim: int = 2):
     """The entry of every *_device wrapper: CUDA tensors or an error naming the host mirror, the dtype and the dimension
     asserted (and equal shapes, unless only the row width has to agree), contiguous copies returned."""
@@ -86,13 +121,21 @@ def retrieval_ranks_device(emb1, emb2, normalize: bool = False, want_sim: bool =
     return r12, r21, met, sim
 
 
-def retrieval_topk_device(queries, gallery, k: int, normalize: bool = False, want_sim: bool = False):
+def retrieval_topk_device(queries, gallery, k: int, normalize: bool = False, want_sim: bool = False, keep=None):
     """queries [M, d], gallery [N, d]: cuda float32.  Returns (idx int32 [M, k], scores float32 [M, k], sim [M, N] or None), all
     on the device (no synchronisation): compute_retrieval_topk of the fp32 similarities retrieval_ranks_device counts on, without
-    the M x N matrix (want_sim is a testing aid).  1 <= k <= min(N, 128)."""
+    the M x N matrix (want_sim is a testing aid).  1 <= k <= min(N, 128).
+    keep: a cuda torch.bool or torch.uint8 tensor [N], nonzero = the row may be returned (coot_retrieval_topk_masked): the bytes of
+    this call on gallery[keep] with the indices mapped back to rows of gallery, compute_retrieval_topk_masked of the similarities;
+    k is still checked against N, and with fewer than k kept rows the tail of every row is idx = -1, score = -inf.  sim holds every
+    similarity, masked rows included.  keep=None: the unfiltered call."""
     import torch
     from . import lib as _lib
-    queries, gallery = _device_pair("retrieval_topk_device", "compute_retrieval_topk", queries, gallery, torch.float32, same_shape=False)
+    if keep is not None:
+        assert gallery.dim() == 2, gallery.shape
+        keep = _check_keep("retrieval_topk_device", keep, gallery.shape[0])
+    queries, gallery = _device_pair("retrieval_topk_device", "compute_retrieval_topk" + ("_masked" if keep is not None else ""), queries, gallery,
+                                    torch.float32, same_shape=False)
     (m, d), n, k = queries.shape, gallery.shape[0], int(k)
     lib = _lib.load()
     dev = queries.device
@@ -100,6 +143,11 @@ def retrieval_topk_device(queries, gallery, k: int, normalize: bool = False, wan
     idx = torch.empty(m, max(k, 0), dtype=torch.int32, device=dev)
     scores = torch.empty(m, max(k, 0), dtype=torch.float32, device=dev)
     sim = torch.empty(m, n, dtype=torch.float32, device=dev) if want_sim else None
+    if keep is not None:
+        _lib.check(lib.coot_retrieval_topk_masked(queries.data_ptr(), gallery.data_ptr(), keep.data_ptr(), m, n, d, k, int(normalize), idx.data_ptr(),
+                                                  scores.data_ptr(), sim.data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(),
+                                                  torch.cuda.current_stream().cuda_stream), "coot_retrieval_topk_masked")
+        return idx, scores, sim
     _lib.check(lib.coot_retrieval_topk(queries.data_ptr(), gallery.data_ptr(), m, n, d, k, int(normalize), idx.data_ptr(), scores.data_ptr(),
                                        sim.data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(),
                                        torch.cuda.current_stream().cuda_stream), "coot_retrieval_topk")
@@ -133,7 +181,19 @@ class GalleryIndex:
     one sweep of the gallery, one row per thread.  M > RETRIEVAL_FEW_MAX on a float32 index goes through retrieval_topk_device
     unchanged, which recomputes the gallery norms on every call; on a 16-bit index it goes through the few-query call in slices of
     16 queries (a query's result does not depend on its batch-mates, and no float32 copy of the gallery is made): ceil(M / 16) sweeps
-    of the gallery, so large query batches are not what 16-bit storage is for."""
+    of the gallery, so large query batches are not what 16-bit storage is for.
+
+    Filtering.  search(..., keep=mask): mask is a cuda torch.bool or torch.uint8 tensor [N], nonzero = the row may be returned; the
+    result is the bytes of the search on an index of gallery[mask] with its indices mapped back (compute_retrieval_topk_masked of the
+    similarities), routed as above (coot_retrieval_topk_few_masked, coot_retrieval_topk_masked).  k is still checked against N only;
+    with fewer than k rows kept, the tail of every row is idx = -1, score = -inf.  sim holds every similarity.  Without sim, blocks
+    of 128 rows (64 on the tile path) that keep nothing are not read at all, so a contiguous subset costs about its share of the
+    sweep and a scattered one costs the whole sweep.
+    remove(rows) / restore(rows=None): a persistent filter held by the index, index.keep: None until the first remove, then a
+    torch.bool [N] on the device (True = searched), written with device operations and no synchronisation.  rows is a sequence of
+    ints or an int tensor; a host sequence (or CPU tensor) with a row outside [0, N) raises IndexError, a device tensor is not
+    checked and its rows outside [0, N) are ignored.  restore() clears the filter.  search combines index.keep with its own keep by
+    logical AND.  Removed rows still occupy memory: the gallery bytes and the norms are untouched, only the selection skips them."""
 
     def __init__(self, gallery, normalize: bool = True, storage=None):
         import torch
@@ -150,6 +210,7 @@ class GalleryIndex:
         self.gallery = gallery.to(self.storage).contiguous()  # (.to() returns the tensor itself when the dtype is its own)
         self._code = codes[self.storage]
         self.normalize = bool(normalize)
+        self.keep = None
         self.norms = None
         if self.normalize:
             n, d = self.gallery.shape
@@ -166,9 +227,48 @@ class GalleryIndex:
         """The bytes the index keeps on the device: the gallery in its storage type and, when normalising, its fp32 row norms."""
         return self.gallery.numel() * self.gallery.element_size() + (self.norms.numel() * 4 if self.norms is not None else 0)
 
-    def search(self, queries, k: int, want_sim: bool = False):
+    def _row_flags(self, fn: str, rows):
+        """torch.bool [N] on the device, True at the given rows."""
+        import torch
+        n, dev = self.gallery.shape[0], self.gallery.device
+        if not (isinstance(rows, torch.Tensor) and rows.is_cuda):
+            r = np.asarray(rows.numpy() if isinstance(rows, torch.Tensor) else rows).reshape(-1)
+            if r.size and r.dtype.kind not in "iu":
+                raise TypeError(f"GalleryIndex.{fn}: rows of dtype {r.dtype}; row numbers are integers")
+            r = r.astype(np.int64)
+            bad = r[(r < 0) | (r >= n)]
+            if bad.size:
+                raise IndexError(f"GalleryIndex.{fn}: row {int(bad[0])} is outside [0, {n})")
+            rows = torch.from_numpy(r).to(dev)
+        elif rows.dtype.is_floating_point or rows.dtype is torch.bool:
+            raise TypeError(f"GalleryIndex.{fn}: rows of dtype {rows.dtype}; row numbers are integers")
+        r = rows.reshape(-1).to(device=dev, dtype=torch.int64)
+        hit = torch.zeros(n + 1, dtype=torch.bool, device=dev)  # slot N takes the rows outside [0, N) of an unchecked device tensor
+        hit[torch.where((r >= 0) & (r < n), r, torch.full_like(r, n))] = True
+        return hit[:n]
+
+    def remove(self, rows):
+        """Rows that later searches do not return, until they are restored."""
+        import torch
+        hit = self._row_flags("remove", rows)
+        if self.keep is None:
+            self.keep = torch.ones(self.gallery.shape[0], dtype=torch.bool, device=self.gallery.device)
+        self.keep &= ~hit
+
+    def restore(self, rows=None):
+        """Makes removed rows searchable again; without an argument all of them (index.keep is None again)."""
+        if rows is None:
+            self.keep = None
+        elif self.keep is not None:
+            self.keep |= self._row_flags("restore", rows)
+        else:
+            self._row_flags("restore", rows)  # (nothing is removed: the rows are checked all the same)
+
+    def search(self, queries, k: int, want_sim: bool = False, keep=None):
         import torch
         from . import lib as _lib
+        if keep is not None:
+            keep = _check_keep("GalleryIndex.search", keep, self.gallery.shape[0])
         if not queries.is_cuda:
             raise RuntimeError("GalleryIndex.search needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk)")
         if queries.dim() == 1:
@@ -180,8 +280,10 @@ class GalleryIndex:
         if not 1 <= k <= min(n, 128):
             raise ValueError(f"GalleryIndex.search: k = {k} is outside 1 .. min(N = {n}, 128)")
         m = queries.shape[0]
+        if self.keep is not None:  # the index's own filter AND the search's
+            keep = self.keep.view(torch.uint8) if keep is None else (self.keep & (keep != 0)).view(torch.uint8)
         if m > RETRIEVAL_FEW_MAX and not self._code:
-            return retrieval_topk_device(queries, self.gallery, k, normalize=self.normalize, want_sim=want_sim)
+            return retrieval_topk_device(queries, self.gallery, k, normalize=self.normalize, want_sim=want_sim, keep=keep)
         queries = queries.contiguous()
         lib = _lib.load()
         dev = queries.device
@@ -191,6 +293,13 @@ class GalleryIndex:
         sim = torch.empty(m, n, dtype=torch.float32, device=dev) if want_sim else None
         norms = self.norms.data_ptr() if self.normalize else None
         st = torch.cuda.current_stream().cuda_stream
+        if keep is not None:
+            for i in range(0, m, RETRIEVAL_FEW_MAX):  # (more than one slice on 16-bit storage only)
+                mm = min(RETRIEVAL_FEW_MAX, m - i)
+                _lib.check(lib.coot_retrieval_topk_few_masked(queries[i:].data_ptr(), self.gallery.data_ptr(), self._code, norms, keep.data_ptr(), mm, n, d,
+                                                              k, idx[i:].data_ptr(), scores[i:].data_ptr(), sim[i:].data_ptr() if want_sim else None,
+                                                              ws.data_ptr(), ws.numel(), st), "coot_retrieval_topk_few_masked")
+            return idx, scores, sim
         if not self._code:
             _lib.check(lib.coot_retrieval_topk_few(queries.data_ptr(), self.gallery.data_ptr(), norms, m, n, d, k, idx.data_ptr(), scores.data_ptr(),
                                                    sim.data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(), st), "coot_retrieval_topk_few")

@@ -398,6 +398,32 @@ int coot_retrieval_topk_few_h(const float* queries, const void* gallery, int gal
                               int d, int K, int32_t* idx_out, float* score_out, float* sim_out, void* workspace, size_t workspace_bytes,
                               coot_stream_t stream);
 
+/* ---- filtered search: a keep mask over the gallery rows ------------------------------------------------------------------
+ * keep: device bytes [N], nonzero = the gallery row may be returned.  A row whose byte is zero is never a candidate: a search
+ * restricted to a subset, or one that skips deleted rows, without copying or renumbering the gallery.  A similarity is the same
+ * FMA chain wherever its row lies and the total order survives a monotone renumbering, so idx_out / score_out are, byte for byte,
+ * the unmasked call on the compacted gallery (the kept rows in order) with its indices mapped back to rows of the full gallery.
+ *   K is validated against N only, 1 <= K <= min(N, 128): counting the mask would need a host synchronisation.  With c < K kept
+ *   rows, slots r >= c of a query hold idx = -1, score = -inf.  (Inside the kernels an unfilled slot is the entry word 0, which is
+ *   a real entry only for a similarity that is the all-ones NaN at gallery row 0: a masked search reports that one as unfilled.)
+ *   sim_out, when given, is not affected by the mask: every similarity, the bytes of the unmasked call.
+ *   sim_out == NULL: a block of rows without a kept one (64 rows in coot_retrieval_topk_masked, 128 in
+ *   coot_retrieval_topk_few_masked) is skipped before its first load: no gallery bytes, no FMAs.  Contiguous masks make a search
+ *   cheaper, scattered ones do not.  Norms, when used, are still those of all N rows.
+ *   keep == NULL: the unmasked kernels, exactly the launches of the unmasked call.
+ * coot_retrieval_topk_masked: coot_retrieval_topk with keep.  coot_retrieval_topk_few_masked: coot_retrieval_topk_few
+ * (gallery_dtype == COOT_GALLERY_F32) or coot_retrieval_topk_few_h (COOT_GALLERY_BF16, COOT_GALLERY_F16) with keep.  The mask
+ * needs no workspace: coot_retrieval_topk_workspace_bytes and coot_retrieval_topk_few_workspace_bytes serve them, and the split
+ * options act as on the unmasked calls.  A refused call (unknown dtype, null pointer other than keep, M or K outside its range,
+ * workspace too small) returns before any launch and writes nothing.  No allocation, no synchronisation; no pointer is retained. */
+#define COOT_GALLERY_F32 0
+int coot_retrieval_topk_masked(const float* queries, const float* gallery, const uint8_t* keep, int M, int N, int d, int K, int normalize,
+                               int32_t* idx_out, float* score_out, float* sim_out, void* workspace, size_t workspace_bytes,
+                               coot_stream_t stream);
+int coot_retrieval_topk_few_masked(const float* queries, const void* gallery, int gallery_dtype, const float* gallery_norms,
+                                   const uint8_t* keep, int M, int N, int d, int K, int32_t* idx_out, float* score_out, float* sim_out,
+                                   void* workspace, size_t workspace_bytes, coot_stream_t stream);
+
 /* ---- labelled retrieval ranking on the device: M queries, N gallery rows, several queries per row -----------------------
  * coot_retrieval_ranks without the assumption "N x N, ground truth on the diagonal": labels[i] (device int32 [M]) is the gallery
  * row of query i.  Several queries may share a row (a second annotation set, several captions per clip), rows may have no query
