@@ -431,6 +431,54 @@ __global__ __launch_bounds__(256) void rt_norms_kernel(const T* a, int Ma, const
   if (lane == 0) { if (row < Ma) na[row] = sqrtf(s); else nb[row - Ma] = sqrtf(s); }
 }
 
+// An fp32 or 16-bit source element as a gallery element of type G (rt_put_kernel).  fp32 -> bfloat16 rounds to nearest even and writes
+// every NaN as 0x7FC0 (what tensor.to(torch.bfloat16) writes); fp32 -> IEEE half is v_cvt_f16_f32 (nearest even, infinities above
+// 65 504); a 16-bit element widens exactly; the same type is moved, never computed on: its bits stay.
+template <typename G> struct Put;
+template <> struct Put<float> {
+  static __device__ __forceinline__ float from(float x) { return x; }
+  static __device__ __forceinline__ float from(unsigned short x) { return widen(x); }
+  static __device__ __forceinline__ float from(_Float16 x) { return widen(x); }
+};
+template <> struct Put<unsigned short> {
+  static __device__ __forceinline__ unsigned short from(unsigned short x) { return x; }
+  static __device__ __forceinline__ unsigned short from(float x) {
+    const unsigned u = __float_as_uint(x);
+    return x != x ? (unsigned short)0x7FC0u : (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+  }
+};
+template <> struct Put<_Float16> {
+  static __device__ __forceinline__ _Float16 from(_Float16 x) { return x; }
+  static __device__ __forceinline__ _Float16 from(float x) { return (_Float16)x; }
+};
+
+// Source row p of src [R, d] becomes row dest[p] (dest == nullptr: row0 + p) of gallery [N, d], and norms[row] (when given) the norm
+// rt_norms_kernel computes on the stored row: one wave per row, four rows per workgroup, row_sumsq on what was stored.  A lane reads
+// back exactly the elements it stored itself (the same striding), so program order is all the ordering the read needs.  A destination
+// outside [0, N) skips the row (the whole wave: the row number is uniform in it).
+template <typename S, typename G>
+__global__ __launch_bounds__(256) void rt_put_kernel(const S* __restrict__ src, int R, int d, const int* __restrict__ dest, int row0, G* gallery,
+                                                     int N, float* norms) {
+  const int lane = threadIdx.x & 63, p = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (p >= R) return;
+  const int row = dest ? dest[p] : row0 + p;
+  if (row < 0 || row >= N) return;
+  const S* s = src + (long)p * d;
+  G* g = gallery + (long)row * d;
+  for (int c = lane; c < d; c += 64) g[c] = Put<G>::from(s[c]);
+  if (norms) {
+    const float sq = row_sumsq((const G*)g, d, lane);
+    if (lane == 0) norms[row] = sqrtf(sq);
+  }
+}
+
+template <typename S, typename G>
+int put_launch(const void* src, int R, int d, const int32_t* dest, int row0, void* gallery, int N, float* norms, hipStream_t st) {
+  hipLaunchKernelGGL((rt_put_kernel<S, G>), dim3((R + 3) / 4), dim3(256), 0, st, (const S*)src, R, d, (const int*)dest, row0, (G*)gallery, N, norms);
+  COOT_CHECK_LAUNCH("rt_put");
+  return 0;
+}
+
 // column splits and the tiles each one walks: every split has at least one tile
 struct TkSplit { int S, tiles; };
 TkSplit tk_split(int M, int N) {
@@ -1232,6 +1280,28 @@ int coot_retrieval_topk_few_masked(const float* queries, const void* gallery, in
     return few_search(fn, queries, (const unsigned short*)gallery, gallery_norms, keep, M, N, d, K, idx_out, score_out, sim_out, workspace,
                       workspace_bytes, st);
   return few_search(fn, queries, (const _Float16*)gallery, gallery_norms, keep, M, N, d, K, idx_out, score_out, sim_out, workspace, workspace_bytes, st);
+}
+
+int coot_retrieval_rows_put(const void* src, int src_dtype, int R, int d, const int32_t* dest, int row0, void* gallery, int gallery_dtype, int N,
+                            float* norms, coot_stream_t stream) {
+  const char* fn = "retrieval_rows_put";
+  const int F = COOT_GALLERY_F32, B = COOT_GALLERY_BF16, H = COOT_GALLERY_F16;
+  COOT_REQUIRE(src && gallery, "%s: null pointer", fn);
+  COOT_REQUIRE(R >= 1 && d >= 1 && N >= 1, "%s: R = %d, d = %d, N = %d", fn, R, d, N);
+  COOT_REQUIRE((src_dtype == F && (gallery_dtype == F || gallery_dtype == B || gallery_dtype == H)) ||
+                   (src_dtype == B && (gallery_dtype == B || gallery_dtype == F)) || (src_dtype == H && (gallery_dtype == H || gallery_dtype == F)),
+               "%s: src_dtype = %d, gallery_dtype = %d (fp32 into any of COOT_GALLERY_F32, _BF16, _F16; a 16-bit type into itself or fp32)", fn,
+               src_dtype, gallery_dtype);
+  if (dest) COOT_REQUIRE(row0 == 0, "%s: row0 = %d with dest (the destinations are dest[p]: row0 has to be 0)", fn, row0);
+  else COOT_REQUIRE(row0 >= 0 && row0 <= N && R <= N - row0, "%s: rows [%d, %d + %d) are not inside [0, %d)", fn, row0, row0, R, N);
+  hipStream_t st = (hipStream_t)stream;
+  if (src_dtype == F && gallery_dtype == F) return put_launch<float, float>(src, R, d, dest, row0, gallery, N, norms, st);
+  if (src_dtype == F && gallery_dtype == B) return put_launch<float, unsigned short>(src, R, d, dest, row0, gallery, N, norms, st);
+  if (src_dtype == F) return put_launch<float, _Float16>(src, R, d, dest, row0, gallery, N, norms, st);
+  if (src_dtype == B && gallery_dtype == B) return put_launch<unsigned short, unsigned short>(src, R, d, dest, row0, gallery, N, norms, st);
+  if (src_dtype == B) return put_launch<unsigned short, float>(src, R, d, dest, row0, gallery, N, norms, st);
+  if (gallery_dtype == H) return put_launch<_Float16, _Float16>(src, R, d, dest, row0, gallery, N, norms, st);
+  return put_launch<_Float16, float>(src, R, d, dest, row0, gallery, N, norms, st);
 }
 
 size_t coot_retrieval_ranks_labeled_workspace_bytes(int M, int N, int d) {

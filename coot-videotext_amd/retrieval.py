@@ -14,6 +14,9 @@ the gallery may be held in bfloat16 or float16 (coot_retrieval_topk_few_h: the b
 Filtered search (compute_retrieval_topk_masked; keep= of retrieval_topk_device and GalleryIndex.search; GalleryIndex.remove /
 restore): a keep flag per gallery row that the selection consults (coot_retrieval_topk_masked, coot_retrieval_topk_few_masked) —
 the bytes of the unfiltered search on gallery[keep] with its indices mapped back, without the copy.
+A gallery that changes (GalleryIndex.add / update / compact): rows appended into spare capacity or overwritten in place together with
+their norms (coot_retrieval_rows_put: O(R d) bytes, no synchronisation), removed rows dropped physically — after any sequence of
+them the index holds, byte for byte, what a fresh index on the same rows holds.
 
 Sharded validation (data-parallel runs): retrieval_ranks_part_device counts one strip of rows, an integer all-reduce of the
 strips is the whole (compute_retrieval_device(dp=...)), retrieval_metrics_device turns rank vectors into the metrics;
@@ -159,10 +162,28 @@ GALLERY_BF16, GALLERY_F16 = 1, 2  # include/coot_hip.h: COOT_GALLERY_BF16, COOT_
 _STORAGE_NAMES = "torch.float32, torch.bfloat16 or torch.float16"
 
 
-class GalleryIndex:
-    """A gallery that stays on the device between searches: a few queries at a time against a corpus that does not change.
+def _gallery_codes():
+    """torch dtype -> COOT_GALLERY_* code."""
+    import torch
+    return {torch.float32: 0, torch.bfloat16: GALLERY_BF16, torch.float16: GALLERY_F16}
 
-    GalleryIndex(gallery, normalize=True, storage=None): gallery is a cuda float32, bfloat16 or float16 [N, d] tensor.
+
+def _host_rows(fn: str, rows, n: int) -> np.ndarray:
+    """Row numbers given on the host (a sequence or a CPU tensor), checked: int64 [R], integers (TypeError) inside [0, n) (IndexError)."""
+    r = np.asarray(rows.numpy() if hasattr(rows, "numpy") else rows).reshape(-1)
+    if r.size and r.dtype.kind not in "iu":
+        raise TypeError(f"GalleryIndex.{fn}: rows of dtype {r.dtype}; row numbers are integers")
+    r = r.astype(np.int64)
+    bad = r[(r < 0) | (r >= n)]
+    if bad.size:
+        raise IndexError(f"GalleryIndex.{fn}: row {int(bad[0])} is outside [0, {n})")
+    return r
+
+
+class GalleryIndex:
+    """A gallery that stays on the device between searches: a few queries at a time against a corpus that changes row by row, if at all.
+
+    GalleryIndex(gallery, normalize=True, storage=None, capacity=None): gallery is a cuda float32, bfloat16 or float16 [N, d] tensor.
     storage=None keeps the tensor's own dtype, by reference when contiguous (a copy otherwise).  storage=torch.bfloat16 or
     torch.float16 on a float32 gallery converts it once (gallery.to(storage): round to nearest even) and the float32 tensor is not
     kept: half the bytes resident, half the bytes every search reads.  storage=torch.float32 on a 16-bit tensor widens it.  Any other
@@ -170,8 +191,8 @@ class GalleryIndex:
     them, and nothing checks for it on the device, so rows that are not normalised are better kept in bfloat16.  index.storage is
     the dtype held, index.nbytes the bytes of the gallery and its norms.
     normalize=True computes the row norms once (coot_retrieval_row_norms, coot_retrieval_row_norms_h) and every search divides by
-    them, as retrieval_topk_device(normalize=True) does.  The index does not watch the tensor: a caller that changes the gallery
-    builds a new index, or searches with stale norms.
+    them, as retrieval_topk_device(normalize=True) does.  The index does not watch the tensor: a caller that writes into a gallery kept
+    by reference searches with stale norms; rows change through add / update (below).
 
     search(queries, k, want_sim=False) returns (idx int32 [M, k], scores float32 [M, k], sim [M, N] or None) on the device, no
     synchronisation: the bytes of retrieval_topk_device(queries, gallery, k, normalize=...), where gallery is the stored one widened
@@ -193,28 +214,52 @@ class GalleryIndex:
     torch.bool [N] on the device (True = searched), written with device operations and no synchronisation.  rows is a sequence of
     ints or an int tensor; a host sequence (or CPU tensor) with a row outside [0, N) raises IndexError, a device tensor is not
     checked and its rows outside [0, N) are ignored.  restore() clears the filter.  search combines index.keep with its own keep by
-    logical AND.  Removed rows still occupy memory: the gallery bytes and the norms are untouched, only the selection skips them."""
+    logical AND.  Removed rows still occupy memory until compact(): the gallery bytes and the norms are untouched, only the selection
+    skips them.
 
-    def __init__(self, gallery, normalize: bool = True, storage=None):
+    Growth.  index.n (= len(index)) rows are searched, index.capacity rows fit the buffer; index.gallery, index.norms and index.keep
+    are the first n rows of it, reassigned whenever n changes (a reference taken earlier keeps the rows it had).  capacity=None is the
+    constructor above (capacity == n); capacity=c >= n allocates [c, d] rows and [c] norms at once and copies the gallery in
+    (c < n: ValueError); nbytes counts the capacity.  add(rows) appends, update(rows, values) overwrites, compact() drops the removed
+    rows and returns their old numbering: see the methods.  After any sequence of them gallery, norms and every search are, byte for
+    byte, those of a fresh index on the same rows.  The index never writes a tensor it did not allocate: the first add or update on
+    a gallery kept by reference moves the rows into a buffer of its own (index.gallery.data_ptr() changes, the caller's bytes stay).
+    add and update do not synchronise; compact does.  Everything runs on the current stream, allocation and growth included: an
+    index is used from one stream at a time."""
+
+    def __init__(self, gallery, normalize: bool = True, storage=None, capacity=None):
         import torch
         from . import lib as _lib
-        codes = {torch.float32: 0, torch.bfloat16: GALLERY_BF16, torch.float16: GALLERY_F16}
+        codes = _gallery_codes()
         if gallery.dtype not in codes:  # (before the device check: the message a caller needs first)
             raise ValueError(f"GalleryIndex: a gallery of dtype {gallery.dtype}; it has to be {_STORAGE_NAMES}")
         if storage is not None and storage not in codes:
             raise ValueError(f"GalleryIndex: storage = {storage}; it has to be {_STORAGE_NAMES} (or None: the gallery's own dtype)")
+        if capacity is not None and gallery.dim() == 2 and int(capacity) < gallery.shape[0]:
+            raise ValueError(f"GalleryIndex: capacity = {capacity} is less than the {gallery.shape[0]} rows of the gallery")
         if not gallery.is_cuda:
             raise RuntimeError("GalleryIndex needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk)")
         assert gallery.dim() == 2 and gallery.shape[0] >= 1 and gallery.shape[1] >= 1, gallery.shape
         self.storage = gallery.dtype if storage is None else storage
-        self.gallery = gallery.to(self.storage).contiguous()  # (.to() returns the tensor itself when the dtype is its own)
         self._code = codes[self.storage]
         self.normalize = bool(normalize)
         self.keep = None
         self.norms = None
+        n, d = gallery.shape
+        # _buf / _nbuf / _kbuf: the [capacity, d] rows, [capacity] norms and [capacity] keep flags the index allocated itself, of which
+        # gallery / norms / keep are the first n.  _buf is None while the gallery is the caller's tensor, kept by reference.
+        self._buf = self._nbuf = self._kbuf = None
+        if capacity is None:
+            self.gallery = gallery.to(self.storage).contiguous()  # (.to() returns the tensor itself when the dtype is its own)
+            if self.gallery.data_ptr() != gallery.data_ptr():
+                self._buf = self.gallery  # a converted or contiguous copy is the index's own
+        else:
+            self._buf = torch.empty(int(capacity), d, dtype=self.storage, device=gallery.device)
+            self._buf[:n].copy_(gallery)  # (the conversion of gallery.to(storage))
+            self.gallery = self._buf[:n]
         if self.normalize:
-            n, d = self.gallery.shape
-            self.norms = torch.empty(n, dtype=torch.float32, device=gallery.device)
+            self._nbuf = torch.empty(self.capacity, dtype=torch.float32, device=gallery.device)
+            self.norms = self._nbuf[:n]
             st = torch.cuda.current_stream().cuda_stream
             if self._code:
                 _lib.check(_lib.load().coot_retrieval_row_norms_h(self.gallery.data_ptr(), self._code, n, d, self.norms.data_ptr(), st),
@@ -223,23 +268,152 @@ class GalleryIndex:
                 _lib.check(_lib.load().coot_retrieval_row_norms(self.gallery.data_ptr(), n, d, self.norms.data_ptr(), st), "coot_retrieval_row_norms")
 
     @property
+    def n(self) -> int:
+        """The rows that are searched."""
+        return self.gallery.shape[0]
+
+    def __len__(self) -> int:
+        return self.gallery.shape[0]
+
+    @property
+    def capacity(self) -> int:
+        """The rows the buffer holds: add() up to here writes the new rows only."""
+        buf = getattr(self, "_buf", None)
+        return self.gallery.shape[0] if buf is None else buf.shape[0]
+
+    @property
     def nbytes(self) -> int:
-        """The bytes the index keeps on the device: the gallery in its storage type and, when normalising, its fp32 row norms."""
-        return self.gallery.numel() * self.gallery.element_size() + (self.norms.numel() * 4 if self.norms is not None else 0)
+        """The bytes the index keeps on the device: the gallery in its storage type and, when normalising, its fp32 row norms —
+        all `capacity` rows of them once the index owns its buffer."""
+        rows = self.capacity
+        return rows * self.gallery.shape[1] * self.gallery.element_size() + (rows * 4 if self.norms is not None else 0)
+
+    def _set_rows(self, n: int):
+        """gallery, norms and keep as views of the first n rows of the index's own buffers."""
+        self.gallery = self._buf[:n]
+        if self.norms is not None:
+            self.norms = self._nbuf[:n]
+        if self.keep is not None:
+            self.keep = self._kbuf[:n]
+
+    def _own(self, rows: int):
+        """Makes the gallery (and norms, and keep flags) live in buffers the index allocated, with room for `rows` rows: the first call
+        on a gallery kept by reference copies it; too small a buffer grows to at least twice its size.  Allocation and copies are
+        ordinary stream-ordered tensor operations on the current stream."""
+        import torch
+        n, d, dev = self.gallery.shape[0], self.gallery.shape[1], self.gallery.device
+        buf, cap = getattr(self, "_buf", None), self.capacity
+        if buf is None or rows > cap:
+            cap = rows if rows <= cap else max(rows, 2 * cap)
+            self._buf = torch.empty(cap, d, dtype=self.gallery.dtype, device=dev)
+            self._buf[:n].copy_(self.gallery)
+            if self.norms is not None:
+                self._nbuf = torch.empty(cap, dtype=torch.float32, device=dev)
+                self._nbuf[:n].copy_(self.norms)
+            self._kbuf = None
+        kbuf = getattr(self, "_kbuf", None)
+        if self.keep is not None and (kbuf is None or kbuf.shape[0] < cap or kbuf.data_ptr() != self.keep.data_ptr()):
+            self._kbuf = torch.ones(cap, dtype=torch.bool, device=dev)
+            self._kbuf[:n].copy_(self.keep)
+        self._set_rows(n)
+
+    def _check_values(self, fn: str, values, rows=None):
+        """The rows given to add / update: float32 or the storage type, [R, d] (or [d]: one row), R == rows where that is fixed
+        (ValueError), on the device (RuntimeError).  Returns them contiguous, as [R, d]."""
+        import torch
+        d = self.gallery.shape[1]
+        if not isinstance(values, torch.Tensor) or values.dtype not in (torch.float32, self.storage):
+            raise ValueError(f"GalleryIndex.{fn}: rows of dtype {getattr(values, 'dtype', type(values).__name__)}; an index held in {self.storage} "
+                             f"takes torch.float32" + ("" if self.storage is torch.float32 else f" or {self.storage}"))
+        if values.dim() == 1:
+            values = values[None]
+        if values.dim() != 2 or values.shape[1] != d:
+            raise ValueError(f"GalleryIndex.{fn}: rows of shape {tuple(values.shape)}, a gallery of width {d} ([R, {d}] or [{d}])")
+        if rows is not None and values.shape[0] != rows:
+            raise ValueError(f"GalleryIndex.{fn}: {values.shape[0]} rows of values for {rows} row numbers")
+        if not values.is_cuda:
+            raise RuntimeError(f"GalleryIndex.{fn} needs CUDA tensors (there is no CPU fallback; build a new index on the host's rows)")
+        return values.contiguous()
+
+    def _put(self, values, dest, row0: int, n_rows: int):
+        import torch
+        from . import lib as _lib
+        _lib.check(_lib.load().coot_retrieval_rows_put(values.data_ptr(), _gallery_codes()[values.dtype], values.shape[0], values.shape[1],
+                                                       None if dest is None else dest.data_ptr(), row0, self._buf.data_ptr(), self._code, n_rows,
+                                                       self._nbuf.data_ptr() if self.norms is not None else None,
+                                                       torch.cuda.current_stream().cuda_stream), "coot_retrieval_rows_put")
+
+    def add(self, rows) -> int:
+        """Appends rows (cuda float32 or index.storage, [R, d] or [d]) as gallery rows n .. n + R - 1 and returns the first new row
+        number, a host integer; nothing is synchronised.  The rows are converted as GalleryIndex(storage=...) converts them and their
+        norms are the ones a fresh index computes (coot_retrieval_rows_put): the grown index is, byte for byte, a fresh index on all
+        rows.  With room in the buffer (index.capacity) this is one launch that writes O(R d) bytes; without, the buffer first grows
+        to at least twice its size.  New rows are searched at once, whatever filter is set."""
+        values = self._check_values("add", rows)
+        n, r = self.gallery.shape[0], values.shape[0]
+        if r == 0:
+            return n
+        self._own(n + r)
+        self._put(values, None, n, self._buf.shape[0])
+        if self.keep is not None:
+            self._kbuf[n:n + r] = True
+        self._set_rows(n + r)
+        return n
+
+    def update(self, rows, values):
+        """Overwrites gallery rows in place: rows follows the conventions of remove() (a host sequence or CPU tensor is checked:
+        IndexError outside [0, n), ValueError for a repeated row; a device int tensor is not: rows outside [0, n) are ignored and of a
+        repeated row the last position wins), values is [len(rows), d] as add() takes them.  Stored bytes and norms become those of a
+        fresh index on the patched gallery.  The filter is not touched: a removed row that is updated stays removed, and comes back with
+        its new value when restored.  No synchronisation."""
+        import torch
+        n, dev = self.gallery.shape[0], self.gallery.device
+        if isinstance(rows, torch.Tensor) and rows.is_cuda:
+            if rows.dtype.is_floating_point or rows.dtype is torch.bool:
+                raise TypeError(f"GalleryIndex.update: rows of dtype {rows.dtype}; row numbers are integers")
+            dest = rows.reshape(-1)
+        else:
+            dest = _host_rows("update", rows, n)
+            if len(np.unique(dest)) != len(dest):
+                raise ValueError("GalleryIndex.update: a row is given more than once")
+        values = self._check_values("update", values, rows=len(dest))
+        if len(dest) == 0:
+            return
+        if isinstance(dest, np.ndarray):
+            dest = torch.from_numpy(dest.astype(np.int32)).to(dev)
+        else:  # of the positions that name one row the highest keeps it and the others become -1; rows outside [0, n) become n: all skipped
+            slot = torch.remainder(dest.to(device=dev, dtype=torch.int64).clamp(-1, n), n + 1)  # in [0, n]: -1 and n are slot n
+            pos = torch.arange(len(slot), device=dev)
+            last = torch.full((n + 1,), -1, dtype=torch.int64, device=dev).scatter_reduce_(0, slot, pos, "amax")
+            dest = torch.where(last[slot] == pos, slot, -1).to(torch.int32)
+        self._own(n)
+        self._put(values, dest, 0, n)
+
+    def compact(self):
+        """Drops the removed rows physically: gallery rows and norms of the kept rows are gathered (not recomputed) into buffers of
+        exactly that size, index.keep becomes None and capacity == n.  Returns old_rows, int32 [n] on the device: the former row
+        number of every row, ascending — old_rows[idx] of a later search names the rows as they were numbered before.  This is the one
+        call of the index that synchronises with the device: the new size is needed on the host.  Without a filter nothing moves and
+        arange(n) is returned; with nothing kept it raises ValueError and changes nothing."""
+        import torch
+        n, dev = self.gallery.shape[0], self.gallery.device
+        if self.keep is None:
+            return torch.arange(n, dtype=torch.int32, device=dev)
+        old = torch.nonzero(self.keep)[:, 0]
+        if old.numel() == 0:
+            raise ValueError("GalleryIndex.compact: every row is removed; an index holds at least one row (restore some, or drop the index)")
+        self._buf = self.gallery[old]
+        self._nbuf = self.norms[old] if self.norms is not None else None
+        self._kbuf = self.keep = None
+        self._set_rows(old.numel())
+        return old.to(torch.int32)
 
     def _row_flags(self, fn: str, rows):
         """torch.bool [N] on the device, True at the given rows."""
         import torch
         n, dev = self.gallery.shape[0], self.gallery.device
         if not (isinstance(rows, torch.Tensor) and rows.is_cuda):
-            r = np.asarray(rows.numpy() if isinstance(rows, torch.Tensor) else rows).reshape(-1)
-            if r.size and r.dtype.kind not in "iu":
-                raise TypeError(f"GalleryIndex.{fn}: rows of dtype {r.dtype}; row numbers are integers")
-            r = r.astype(np.int64)
-            bad = r[(r < 0) | (r >= n)]
-            if bad.size:
-                raise IndexError(f"GalleryIndex.{fn}: row {int(bad[0])} is outside [0, {n})")
-            rows = torch.from_numpy(r).to(dev)
+            rows = torch.from_numpy(_host_rows(fn, rows, n)).to(dev)
         elif rows.dtype.is_floating_point or rows.dtype is torch.bool:
             raise TypeError(f"GalleryIndex.{fn}: rows of dtype {rows.dtype}; row numbers are integers")
         r = rows.reshape(-1).to(device=dev, dtype=torch.int64)

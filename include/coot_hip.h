@@ -424,6 +424,24 @@ int coot_retrieval_topk_few_masked(const float* queries, const void* gallery, in
                                    const uint8_t* keep, int M, int N, int d, int K, int32_t* idx_out, float* score_out, float* sim_out,
                                    void* workspace, size_t workspace_bytes, coot_stream_t stream);
 
+/* ---- a prepared gallery that changes: rows written in place, their norms with them ---------------------------------------
+ * coot_retrieval_rows_put writes the R rows of src [R, d] into the buffer gallery [N, d] and, where norms != NULL, norms[row] of
+ * every row it wrote: what a corpus that grows (rows appended into spare capacity) or is re-encoded (rows overwritten) needs,
+ * O(R d) bytes instead of a new gallery.  One launch, no workspace, no allocation, no synchronisation; no pointer is retained.
+ *   dest == NULL: source row p goes to gallery row row0 + p; 0 <= row0 and row0 + R <= N.
+ *   dest != NULL (device int32 [R]): source row p goes to row dest[p]; a dest[p] outside [0, N) skips that row; row0 has to be 0.
+ *   Two positions with the same destination race: which one stays, and whether the row is one of them at all, is unspecified.
+ *   src_dtype / gallery_dtype: COOT_GALLERY_F32, _BF16, _F16.  Allowed: fp32 into any of the three, bfloat16 into bfloat16 or fp32,
+ *   IEEE half into IEEE half or fp32.  The stored bytes are those of torch's src.to(gallery dtype) for every element that is not a
+ *   NaN: fp32 -> 16 bits rounds to nearest even (bfloat16: every NaN becomes 0x7FC0; IEEE half: the hardware conversion, values
+ *   above 65 504 become infinities), a 16-bit element widens exactly, the same type is copied bit for bit.  A NaN stays a NaN.
+ *   norms[row] has the bits coot_retrieval_row_norms (fp32 gallery) / coot_retrieval_row_norms_h (16-bit) compute on the stored row:
+ *   the sum runs over the stored (rounded) values in the same order, not over the fp32 source.  Slots of rows not written stay.
+ * src and gallery must not overlap (undefined otherwise).  A refused call (null src or gallery, R, d or N < 1, a type pair that
+ * is not allowed, rows outside the buffer, row0 != 0 with dest) returns before any launch and writes nothing. */
+int coot_retrieval_rows_put(const void* src, int src_dtype, int R, int d, const int32_t* dest, int row0, void* gallery, int gallery_dtype,
+                            int N, float* norms, coot_stream_t stream);
+
 /* ---- labelled retrieval ranking on the device: M queries, N gallery rows, several queries per row -----------------------
  * coot_retrieval_ranks without the assumption "N x N, ground truth on the diagonal": labels[i] (device int32 [M]) is the gallery
  * row of query i.  Several queries may share a row (a second annotation set, several captions per clip), rows may have no query
