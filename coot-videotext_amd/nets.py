@@ -263,6 +263,10 @@ class _NetFn(torch.autograd.Function):
         feats, lengths, hid, feats2, lengths2 = ctx.feats, ctx.lengths, ctx.hid, ctx.feats2, ctx.lengths2
         N, L, Din = feats.shape
         N2, L2 = (feats2.shape[0], feats2.shape[1]) if feats2 is not None else (0, 0)
+        if feats2 is not None and not net.cfg.use_input_fc:
+            # coot_net_bwd runs the input LayerNorm's backward of such a network as one launch over all token rows of `feats`: with a
+            # second segment it would read past the end of that tensor (csrc/api.hip)
+            raise RuntimeError("the backward of forward_pair needs a network with input_fc (two segments, one input tensor each)")
         dev = feats.device
         dpooled = dpooled.contiguous().float()
         # gradient sink: the network's persistent flat arena (train_step; param.grad are views of it) or a

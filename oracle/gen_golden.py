@@ -605,6 +605,22 @@ def gen_bench_yc2_2d3d_2816():
              full_grads=False, ragged=False, cc_weight=0.001, sub_step=197, store_reshape=False, train=dict(p=0.1, step_seed=2816001))
 
 
+LONG_PAR = dict(dims=ANET_DIMS, B=8, counts=[4] * 8, Ls=(144, 80, 160, 30), seed=101, full_grads=False, ragged=True, sub_step=197,
+                store_reshape=False)
+
+
+def gen_bench_long_par():
+    """Sequences above 128 rows (a paragraph is the concatenation of its sentences' words, coot/dataset_retrieval.py:128-131): videos of
+    up to 144 frames, paragraphs of up to 160 words next to 80-frame clips and 30-word sentences.  Each local network call then has one
+    segment on the long attention kernels and one on the short ones (tests/test_gpu_long_seq.py)."""
+    gen_full("bench_long_par", **LONG_PAR)
+
+
+def gen_bench_long_par_train():
+    """... in TRAIN mode with the library's masks (p = 0.1): pins the long kernels' attention-dropout masks, forward against backward."""
+    gen_full("bench_long_par_train", train=dict(p=0.1, step_seed=1441601), **LONG_PAR)
+
+
 RK_DIMS = (2048, 1536, 384, 8, 384, 768)
 RK_N, RK_BATCH, RK_LS = 1024, 64, (40, 40, 32, 12)   # validation videos, batch, (Lv, Lc, Lp, Ls)
 RK_EVAL = (4.0, 32, 0.3)    # validation set: feature noise, latent clusters, individual spread (make_latent_batch) — hard enough
@@ -926,6 +942,8 @@ def main():
     gen_bench_hbm_stress_train()
     gen_bench_yc2_100m_2layer_train()
     gen_bench_yc2_2d3d_2816()
+    gen_bench_long_par()
+    gen_bench_long_par_train()
     gen_traj_small()
     gen_traj_small_eps()
     gen_traj_anet()

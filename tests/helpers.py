@@ -151,6 +151,32 @@ def grad_report(named_got, ref: dict, cos_min=0.99, ratio_tol=0.05):
     return bad, "\n".join(rows)
 
 
+def row_report(got, ref, valid, bound=None, small=0.01):
+    """Row-wise comparison of a gradient wrt token rows (dfeats [N, L, D], dhidden [N, D]) with a reference: a lost tile, a mask
+    edge or a segment offset makes SPECIFIC rows wrong by O(1), which a flat cosine over the whole tensor hardly sees.
+    got / ref: [..., D]; valid: boolean mask over the leading dimensions (padding rows carry no gradient that matters).
+    Per valid row e = ||got - ref|| / ||ref||.  A row whose ||ref|| is below `small` x the largest valid row norm has no direction
+    worth comparing: it is checked by magnitude only, e = ||got - ref|| / (small x the largest norm).
+    Returns (worst e, the offending rows, share of magnitude-only rows among the valid ones).  The offending rows are the flat
+    indices (n L + l: the row's place in the padded token matrix, which names the sequence and the tile) of the rows with e > bound,
+    worst first; without a bound, the worst row alone."""
+    ref = np.asarray(ref, np.float64)
+    got = np.asarray(got, np.float64).reshape(ref.shape)
+    D = ref.shape[-1]
+    valid = np.asarray(valid, bool).reshape(-1)
+    ref, got = ref.reshape(-1, D), got.reshape(-1, D)
+    assert valid.shape[0] == ref.shape[0] and valid.any()
+    idx = np.flatnonzero(valid)
+    nr = np.sqrt((ref[idx] ** 2).sum(-1))
+    floor = small * nr.max()
+    mag_only = nr < floor
+    e = np.sqrt(((got[idx] - ref[idx]) ** 2).sum(-1)) / np.where(mag_only, floor, nr)
+    e = np.where(np.isfinite(e), e, np.inf)  # (a NaN row is the worst row, not an ignored one)
+    order = np.argsort(-e, kind="stable")
+    order = order[:1] if bound is None else order[e[order] > bound]
+    return float(e.max()), idx[order], float(mag_only.mean())
+
+
 def rank_flips(e1, e2, r1, r2):
     """Retrieval ranks (nntrainer/retrieval.py:68-98: number of items scored above the paired one) of the L2-normalised embedding
     sets (e1, e2) against those of the reference's (r1, r2), both directions.  Returns (number of (query, item) comparisons whose
