@@ -667,7 +667,7 @@ extern "C" int coot_step_det_seg_flush_get(void);
 extern "C" int coot_internal_stage_hits(void);
 extern "C" int coot_internal_stream_counter(int which);  // api_step.hip: StreamPicker
 extern "C++" { namespace coot { int det_bypass_count(); int det_overflow_count(); int det_set_overflow_guard(int on); int det_overflow_guard(); } }  // det.hip
-extern "C++" { namespace coot { void set_rt_topk_splits(int n); int get_rt_topk_splits(); void set_rt_few_splits(int n); int get_rt_few_splits(); } }  // retrieval.hip
+extern "C++" { namespace coot { void set_rt_topk_splits(int n); int get_rt_topk_splits(); void set_rt_few_splits(int n); int get_rt_few_splits(); } }  // retrieval_tile.hip, retrieval_few.hip
 int coot_get_option(const char* name, int* value) {
   if (!value) { set_error("get_option: null result"); return -1; }
   if (!strcmp(name, "tn_dma")) { *value = get_tn_dma(); return 0; }

@@ -1,0 +1,134 @@
+// What the retrieval sources share (retrieval_tile.hip, retrieval_few.hip, retrieval_index.hip): the chunk constants and the widening of a
+// gallery element, the 64-bit top-K entry and the fold of candidates into a sorted list, and the host helpers that carve a workspace
+// and turn a run-time value into a template argument.  Every kernel is instantiated in one file only.
+#pragma once
+#include <type_traits>
+#include "../../include/coot_hip.h"
+#include "common.h"
+
+namespace coot {
+
+// rt_norms_kernel<float> (retrieval_index.hip) on rows [0, Ma) of a, then [0, Nb) of b; the caller checks the launch
+void rt_launch_norms(const float* a, int Ma, const float* b, int Nb, int d, float* na, float* nb, hipStream_t st);
+
+namespace {
+
+constexpr int RT = 64;   // tile: 64 rows of emb1 x 64 rows of emb2
+constexpr int RK = 32;   // k chunk
+constexpr int RP = RK + 1;
+
+// A gallery element as fp32: itself, a bfloat16 (unsigned short: the upper half of the fp32 word) or an IEEE half (v_cvt_f32_f16).
+// Both 16-bit formats widen exactly, so whatever follows sees the operands of the widened fp32 copy.
+__device__ __forceinline__ float widen(float x) { return x; }
+__device__ __forceinline__ float widen(unsigned short x) { return __uint_as_float((unsigned)x << 16); }
+__device__ __forceinline__ float widen(_Float16 x) { return (float)x; }
+// half e (0 = low) of a 32-bit word that holds two 16-bit elements
+template <typename T>
+__device__ __forceinline__ float widen_half(unsigned w, int e) {
+  const unsigned short b = (unsigned short)(e ? w >> 16 : w & 0xFFFFu);
+  return widen(__builtin_bit_cast(T, b));
+}
+
+// sum x^2 of one row by one wave: the norm of rt_normalize_kernel and of rt_norms_kernel is this sum's sqrtf
+template <typename T>
+__device__ __forceinline__ float row_sumsq(const T* src, int d, int lane) {
+  float s = 0.f;
+  for (int c = lane; c < d; c += 64) { const float x = widen(src[c]); s += x * x; }
+  return wave_sum(s);
+}
+
+// ---- the top-K entry ------------------------------------------------------------------------------------------------------------
+// An entry is one 64-bit word, (order-preserving image of the score) << 32 | column: "ahead" is one unsigned compare, a strict
+// total order over every bit pattern (NaNs included), so selection and merge cannot depend on who came first.
+constexpr int TK_MAX = 128;  // K
+typedef unsigned long long tk_entry_t;
+__device__ __forceinline__ tk_entry_t tk_pack(float s, int j) {
+  unsigned u = __float_as_uint(s + 0.0f);  // -0 -> +0: equal scores, as numpy compares them
+  u ^= (unsigned)((int)u >> 31) | 0x80000000u;
+  return ((tk_entry_t)u << 32) | (unsigned)j;
+}
+__device__ __forceinline__ float tk_score(tk_entry_t e) {
+  const unsigned u = (unsigned)(e >> 32);
+  return __uint_as_float(u ^ ((u & 0x80000000u) ? 0x80000000u : 0xFFFFFFFFu));
+}
+// number of entries ahead of v in a list sorted best first
+__device__ __forceinline__ int tk_ahead(const tk_entry_t* L, int n, tk_entry_t v) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (L[mid] > v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// One wave folds nc <= 64 candidates C into the sorted list L of n entries, of which the K best stay: the new position of an entry
+// is the number of entries ahead of it.  read() takes every entry and counts; place() writes them after a barrier of the waves
+// that share the list (every entry is read before one is placed).
+struct TkFold {
+  tk_entry_t ec, e0, e1;
+  int pc, p0, p1;
+  bool hc, h0, h1;
+  __device__ __forceinline__ void read(const tk_entry_t* L, int n, const tk_entry_t* C, int nc, int lane) {
+    hc = lane < nc; h0 = lane < n; h1 = lane + 64 < n;
+    ec = 0ull; e0 = 0ull; e1 = 0ull;
+    pc = 0; p0 = lane; p1 = lane + 64;
+    if (nc) {
+      if (hc) { ec = C[lane]; pc = tk_ahead(L, n, ec); }
+      if (h0) e0 = L[lane];
+      if (h1) e1 = L[lane + 64];
+      for (int q = 0; q < nc; ++q) {
+        const tk_entry_t v = C[q];
+        pc += v > ec; p0 += v > e0; p1 += v > e1;
+      }
+    }
+  }
+  __device__ __forceinline__ void place(tk_entry_t* L, int K) const {
+    if (hc && pc < K) L[pc] = ec;
+    if (h0 && p0 < K) L[p0] = e0;
+    if (h1 && p1 < K) L[p1] = e1;
+  }
+};
+
+// The result of an unfilled slot in the masked searches (fewer than K kept rows): index -1, score -inf.  Word 0 is a real entry
+// only for the all-ones NaN at column 0 (tk_pack), which a masked search therefore reports as unfilled.
+__device__ __forceinline__ int tk_idx_masked(tk_entry_t e) { return e ? (int)(unsigned)e : -1; }
+__device__ __forceinline__ float tk_score_masked(tk_entry_t e) { return e ? tk_score(e) : __uint_as_float(0xFF800000u); }
+
+// ---- host helpers ---------------------------------------------------------------------------------------------------------------
+// A workspace carved into consecutive pieces, each rounded up to 256 bytes.  A null base sizes a layout: every piece is nullptr
+// and off is the bytes a real base has to hold.
+struct Arena {
+  char* base;
+  size_t off = 0;
+  template <typename T>
+  T* take(size_t count) { T* p = base ? (T*)(base + off) : nullptr; off += (count * sizeof(T) + 255) & ~(size_t)255; return p; }
+};
+
+// A run-time value as a template argument: f is a generic lambda that receives it as a std::bool_constant, a std::integral_constant
+// or (an element type) an ElemType, and what f returns is returned.
+template <typename F>
+auto with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <typename F>
+auto with_bool(bool a, bool b, F&& f) {
+  return with_bool(a, [&](auto ta) { return with_bool(b, [&](auto tb) { return f(ta, tb); }); });
+}
+// mq: the 1, 2, 4, 8 or 16 accumulators of rt_few_kernel
+template <typename F>
+auto with_mq(int mq, F&& f) {
+  switch (mq) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: return f(std::integral_constant<int, 16>{});
+  }
+}
+// code: COOT_GALLERY_F32, _BF16 (unsigned short) or _F16, which the caller has checked
+template <typename T> struct ElemType { using type = T; };
+template <typename F>
+auto with_elem(int code, F&& f) {
+  return code == COOT_GALLERY_F32 ? f(ElemType<float>{}) : code == COOT_GALLERY_BF16 ? f(ElemType<unsigned short>{}) : f(ElemType<_Float16>{});
+}
+
+}  // namespace
+}  // namespace coot

@@ -7,13 +7,15 @@ compute_retrieval_device: the same results for embeddings that live on the MI355
 in four launches, the N x N matrix is never materialised).  No CPU fallback: CUDA tensors in, device kernels or an error.
 
 compute_retrieval_topk / retrieval_topk_device: WHICH gallery items a query retrieves (the reference returns top1 only), for M
-queries against N gallery rows, M and N independent: the host mirror on a similarity matrix, and coot_retrieval_topk on the
-device (similarities and selection fused, no M x N matrix).  GalleryIndex: the same search for a few queries at a time on a
-gallery that stays on the device, its row norms computed once (coot_retrieval_topk_few: the same bytes, one sweep of the gallery);
-the gallery may be held in bfloat16 or float16 (coot_retrieval_topk_few_h: the bytes of the search on the gallery widened to fp32).
+queries against N gallery rows, M and N independent: the host mirror on a similarity matrix, and the tile search on the device
+(similarities and selection fused, no M x N matrix).  GalleryIndex: the same search for a few queries at a time on a gallery that
+stays on the device, its row norms computed once (the few-query search: the same bytes, one sweep of the gallery); the gallery may
+be held in bfloat16 or float16 (the bytes of the search on the gallery widened to fp32).
 Filtered search (compute_retrieval_topk_masked; keep= of retrieval_topk_device and GalleryIndex.search; GalleryIndex.remove /
-restore): a keep flag per gallery row that the selection consults (coot_retrieval_topk_masked, coot_retrieval_topk_few_masked) —
-the bytes of the unfiltered search on gallery[keep] with its indices mapped back, without the copy.
+restore): a keep flag per gallery row that the selection consults — the bytes of the unfiltered search on gallery[keep] with its
+indices mapped back, without the copy.  Each search is one library call whatever the arguments: coot_retrieval_topk_masked (tile) and
+coot_retrieval_topk_few_masked (few queries, any storage), which with keep = NULL launch what coot_retrieval_topk,
+coot_retrieval_topk_few and coot_retrieval_topk_few_h launch.
 A gallery that changes (GalleryIndex.add / update / compact): rows appended into spare capacity or overwritten in place together with
 their norms (coot_retrieval_rows_put: O(R d) bytes, no synchronisation), removed rows dropped physically — after any sequence of
 them the index holds, byte for byte, what a fresh index on the same rows holds.
@@ -124,14 +126,22 @@ def retrieval_ranks_device(emb1, emb2, normalize: bool = False, want_sim: bool =
     return r12, r21, met, sim
 
 
+def _topk_buffers(ws_bytes: int, m: int, n: int, k: int, want_sim: bool, dev):
+    """What a top-K call writes: (workspace bytes, idx int32 [M, k], scores float32 [M, k], sim float32 [M, N] or None), uninitialised."""
+    import torch
+    return (torch.empty(ws_bytes, dtype=torch.uint8, device=dev), torch.empty(m, max(k, 0), dtype=torch.int32, device=dev),
+            torch.empty(m, max(k, 0), dtype=torch.float32, device=dev), torch.empty(m, n, dtype=torch.float32, device=dev) if want_sim else None)
+
+
 def retrieval_topk_device(queries, gallery, k: int, normalize: bool = False, want_sim: bool = False, keep=None):
     """queries [M, d], gallery [N, d]: cuda float32.  Returns (idx int32 [M, k], scores float32 [M, k], sim [M, N] or None), all
     on the device (no synchronisation): compute_retrieval_topk of the fp32 similarities retrieval_ranks_device counts on, without
     the M x N matrix (want_sim is a testing aid).  1 <= k <= min(N, 128).
-    keep: a cuda torch.bool or torch.uint8 tensor [N], nonzero = the row may be returned (coot_retrieval_topk_masked): the bytes of
+    keep: a cuda torch.bool or torch.uint8 tensor [N], nonzero = the row may be returned: the bytes of
     this call on gallery[keep] with the indices mapped back to rows of gallery, compute_retrieval_topk_masked of the similarities;
     k is still checked against N, and with fewer than k kept rows the tail of every row is idx = -1, score = -inf.  sim holds every
-    similarity, masked rows included.  keep=None: the unfiltered call."""
+    similarity, masked rows included.  keep=None: the unfiltered search.  Either way one call of coot_retrieval_topk_masked, which
+    without keep launches the kernels of coot_retrieval_topk."""
     import torch
     from . import lib as _lib
     if keep is not None:
@@ -141,19 +151,10 @@ def retrieval_topk_device(queries, gallery, k: int, normalize: bool = False, wan
                                     torch.float32, same_shape=False)
     (m, d), n, k = queries.shape, gallery.shape[0], int(k)
     lib = _lib.load()
-    dev = queries.device
-    ws = torch.empty(lib.coot_retrieval_topk_workspace_bytes(m, n, d, k), dtype=torch.uint8, device=dev)
-    idx = torch.empty(m, max(k, 0), dtype=torch.int32, device=dev)
-    scores = torch.empty(m, max(k, 0), dtype=torch.float32, device=dev)
-    sim = torch.empty(m, n, dtype=torch.float32, device=dev) if want_sim else None
-    if keep is not None:
-        _lib.check(lib.coot_retrieval_topk_masked(queries.data_ptr(), gallery.data_ptr(), keep.data_ptr(), m, n, d, k, int(normalize), idx.data_ptr(),
-                                                  scores.data_ptr(), sim.data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(),
-                                                  torch.cuda.current_stream().cuda_stream), "coot_retrieval_topk_masked")
-        return idx, scores, sim
-    _lib.check(lib.coot_retrieval_topk(queries.data_ptr(), gallery.data_ptr(), m, n, d, k, int(normalize), idx.data_ptr(), scores.data_ptr(),
-                                       sim.data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(),
-                                       torch.cuda.current_stream().cuda_stream), "coot_retrieval_topk")
+    ws, idx, scores, sim = _topk_buffers(lib.coot_retrieval_topk_workspace_bytes(m, n, d, k), m, n, k, want_sim, queries.device)
+    _lib.check(lib.coot_retrieval_topk_masked(queries.data_ptr(), gallery.data_ptr(), None if keep is None else keep.data_ptr(), m, n, d, k,
+                                              int(normalize), idx.data_ptr(), scores.data_ptr(), sim.data_ptr() if want_sim else None, ws.data_ptr(),
+                                              ws.numel(), torch.cuda.current_stream().cuda_stream), "coot_retrieval_topk_masked")
     return idx, scores, sim
 
 
@@ -198,15 +199,15 @@ class GalleryIndex:
     synchronisation: the bytes of retrieval_topk_device(queries, gallery, k, normalize=...), where gallery is the stored one widened
     to float32 — a 16-bit value widens exactly, so only the storage differs, not the arithmetic or the order.  queries are float32;
     queries [d] is one query.  1 <= k <= min(N, 128).
-    M <= RETRIEVAL_FEW_MAX goes through coot_retrieval_topk_few (coot_retrieval_topk_few_h on 16-bit storage) with the stored norms:
-    one sweep of the gallery, one row per thread.  M > RETRIEVAL_FEW_MAX on a float32 index goes through retrieval_topk_device
+    M <= RETRIEVAL_FEW_MAX goes through coot_retrieval_topk_few_masked (any storage; without a filter it launches the kernels of
+    coot_retrieval_topk_few / coot_retrieval_topk_few_h) with the stored norms: one sweep of the gallery, one row per thread.  M > RETRIEVAL_FEW_MAX on a float32 index goes through retrieval_topk_device
     unchanged, which recomputes the gallery norms on every call; on a 16-bit index it goes through the few-query call in slices of
     16 queries (a query's result does not depend on its batch-mates, and no float32 copy of the gallery is made): ceil(M / 16) sweeps
     of the gallery, so large query batches are not what 16-bit storage is for.
 
     Filtering.  search(..., keep=mask): mask is a cuda torch.bool or torch.uint8 tensor [N], nonzero = the row may be returned; the
     result is the bytes of the search on an index of gallery[mask] with its indices mapped back (compute_retrieval_topk_masked of the
-    similarities), routed as above (coot_retrieval_topk_few_masked, coot_retrieval_topk_masked).  k is still checked against N only;
+    similarities), routed as above.  k is still checked against N only;
     with fewer than k rows kept, the tail of every row is idx = -1, score = -inf.  sim holds every similarity.  Without sim, blocks
     of 128 rows (64 on the tile path) that keep nothing are not read at all, so a contiguous subset costs about its share of the
     sweep and a scattered one costs the whole sweep.
@@ -460,29 +461,16 @@ class GalleryIndex:
             return retrieval_topk_device(queries, self.gallery, k, normalize=self.normalize, want_sim=want_sim, keep=keep)
         queries = queries.contiguous()
         lib = _lib.load()
-        dev = queries.device
-        ws = torch.empty(lib.coot_retrieval_topk_few_workspace_bytes(min(m, RETRIEVAL_FEW_MAX), n, d, k), dtype=torch.uint8, device=dev)
-        idx = torch.empty(m, k, dtype=torch.int32, device=dev)
-        scores = torch.empty(m, k, dtype=torch.float32, device=dev)
-        sim = torch.empty(m, n, dtype=torch.float32, device=dev) if want_sim else None
+        ws, idx, scores, sim = _topk_buffers(lib.coot_retrieval_topk_few_workspace_bytes(min(m, RETRIEVAL_FEW_MAX), n, d, k), m, n, k, want_sim,
+                                             queries.device)
         norms = self.norms.data_ptr() if self.normalize else None
         st = torch.cuda.current_stream().cuda_stream
-        if keep is not None:
-            for i in range(0, m, RETRIEVAL_FEW_MAX):  # (more than one slice on 16-bit storage only)
-                mm = min(RETRIEVAL_FEW_MAX, m - i)
-                _lib.check(lib.coot_retrieval_topk_few_masked(queries[i:].data_ptr(), self.gallery.data_ptr(), self._code, norms, keep.data_ptr(), mm, n, d,
-                                                              k, idx[i:].data_ptr(), scores[i:].data_ptr(), sim[i:].data_ptr() if want_sim else None,
-                                                              ws.data_ptr(), ws.numel(), st), "coot_retrieval_topk_few_masked")
-            return idx, scores, sim
-        if not self._code:
-            _lib.check(lib.coot_retrieval_topk_few(queries.data_ptr(), self.gallery.data_ptr(), norms, m, n, d, k, idx.data_ptr(), scores.data_ptr(),
-                                                   sim.data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(), st), "coot_retrieval_topk_few")
-            return idx, scores, sim
-        for i in range(0, m, RETRIEVAL_FEW_MAX):  # one slice unless M > RETRIEVAL_FEW_MAX; the calls of a stream run in order: one workspace
+        for i in range(0, m, RETRIEVAL_FEW_MAX):  # one slice unless M > RETRIEVAL_FEW_MAX (16-bit storage only); the calls of a stream run in order: one workspace
             mm = min(RETRIEVAL_FEW_MAX, m - i)
-            _lib.check(lib.coot_retrieval_topk_few_h(queries[i:].data_ptr(), self.gallery.data_ptr(), self._code, norms, mm, n, d, k,
-                                                     idx[i:].data_ptr(), scores[i:].data_ptr(), sim[i:].data_ptr() if want_sim else None,
-                                                     ws.data_ptr(), ws.numel(), st), "coot_retrieval_topk_few_h")
+            _lib.check(lib.coot_retrieval_topk_few_masked(queries[i:].data_ptr(), self.gallery.data_ptr(), self._code, norms,
+                                                          None if keep is None else keep.data_ptr(), mm, n, d, k, idx[i:].data_ptr(),
+                                                          scores[i:].data_ptr(), sim[i:].data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(), st),
+                       "coot_retrieval_topk_few_masked")
         return idx, scores, sim
 
 

@@ -9,6 +9,8 @@ import os
 import numpy as np
 import pytest
 
+from tests.retrieval_cases import bytes_equal as _bytes_equal, planted as _planted, unit as _unit
+
 pytestmark = pytest.mark.gpu
 
 # (M, N, d): one tile; partial tiles on either side with M > N and M < N; ~8 positives per column over several row tiles of one
@@ -25,14 +27,6 @@ def env():
     return torch, cva
 
 
-def _planted(m, n, dim, seed):
-    """The recipe of tests/test_gpu_topk.py: random gallery rows, query i planted on gallery row i mod N."""
-    rs = np.random.RandomState(seed)
-    g = rs.randn(n, dim).astype(np.float32)
-    q = (0.35 * g[np.arange(m) % n] + rs.randn(m, dim)).astype(np.float32)
-    return q, g
-
-
 def _labels(m, n, seed):
     """i mod N, a random tenth redirected to random rows, a few without ground truth."""
     rs = np.random.RandomState(seed)
@@ -42,14 +36,6 @@ def _labels(m, n, seed):
     if m > 1:
         lab[rs.choice(m, size=max(1, m // 40), replace=False)] = -1
     return lab
-
-
-def _unit(x):
-    return x / np.sqrt((x * x).sum(-1, keepdims=True))
-
-
-def _bytes_equal(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def _run(torch, q, g, lab, normalize, want_sim=False):

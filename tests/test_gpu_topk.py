@@ -11,6 +11,8 @@ import pytest
 
 from oracle import coot_oracle as O
 
+from tests.retrieval_cases import bytes_equal as _bytes_equal, check_against_mirror as _check_against_mirror, planted as _planted, unit as _unit
+
 pytestmark = pytest.mark.gpu
 
 
@@ -33,31 +35,6 @@ def splits(env):
         assert lib.coot_set_option(b"rt_topk_splits", n) == 0
     yield set_
     set_(0)
-
-
-def _planted(m, n, dim, seed):
-    """The recipe of tests/test_retrieval_device.py (random rows with a planted match, so the best items are neither random nor
-    trivial), for M != N: query i is planted on gallery row i mod N."""
-    rs = np.random.RandomState(seed)
-    g = rs.randn(n, dim).astype(np.float32)
-    q = (0.35 * g[np.arange(m) % n] + rs.randn(m, dim)).astype(np.float32)
-    return q, g
-
-
-def _unit(x):
-    return x / np.sqrt((x * x).sum(-1, keepdims=True))
-
-
-def _bytes_equal(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def _check_against_mirror(idx, sc, sim, k):
-    from coot_videotext_amd.retrieval import compute_retrieval_topk
-    want_idx, want_sc = compute_retrieval_topk(sim, k)
-    assert idx.dtype == np.int32 and sc.dtype == np.float32 and idx.shape == sc.shape == (sim.shape[0], k)
-    assert np.array_equal(idx, want_idx), np.argwhere(idx != want_idx)[:5]
-    assert np.array_equal(sc, want_sc) and np.array_equal(sc, np.take_along_axis(sim, idx.astype(np.int64), axis=1))
 
 
 @pytest.mark.parametrize("normalize", [True, False])

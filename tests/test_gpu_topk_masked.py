@@ -7,6 +7,8 @@ is for byte equality.  Helpers and the planted-gallery recipe are those of tests
 import numpy as np
 import pytest
 
+from tests.retrieval_cases import bytes_equal as _bytes_equal, host as _host, planted as _planted
+
 pytestmark = pytest.mark.gpu
 
 PATHS = ["tile", "float32", "bfloat16", "float16"]  # retrieval_topk_device, and GalleryIndex on the three storages
@@ -37,31 +39,6 @@ def splits(env):
         assert lib.coot_set_option(b"rt_topk_splits", n) == 0 and lib.coot_set_option(b"rt_few_splits", n) == 0
     yield set_
     set_(0)
-
-
-_PLANTED = {}
-
-
-def _planted(m, n, dim, seed):
-    """Random rows, query i planted on gallery row i mod N.  Made once per shape and seed and shared (read only)."""
-    key = (m, n, dim, seed)
-    if key not in _PLANTED:
-        rs = np.random.RandomState(seed)
-        g = rs.randn(n, dim).astype(np.float32)
-        q = (0.35 * g[np.arange(m) % n] + rs.randn(m, dim)).astype(np.float32)
-        q.setflags(write=False)
-        g.setflags(write=False)
-        _PLANTED[key] = (q, g)
-    return _PLANTED[key]
-
-
-def _bytes_equal(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def _host(torch, *tensors):
-    torch.cuda.synchronize()
-    return [t.cpu().numpy() for t in tensors]
 
 
 def _masks(n, seed):

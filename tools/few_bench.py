@@ -8,44 +8,18 @@ box; medians.  Arms: (a) the tile call, timed TWICE per round so that its own ru
 the microarchitecture notes); the small gallery (27.6 MB) fits the caches, so its floor is reported but proves nothing.
 Acceptance is (b) against (a): faster by more than (a)'s spread = |median a1 - median a2|, and than its min-max range.
 Usage: python tools/few_bench.py [--calls 20] [--warmup 5] [--out profiles/<tag>_topk_few.json]"""
-import argparse
 import json
-import os
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
+from _retrieval_bench import alternate, finish, same, start, stats
 import torch
-import coot_videotext_amd as cva
 from coot_videotext_amd.retrieval import GalleryIndex, retrieval_topk_device
 
 HBM_STREAM_BYTES_PER_S = 6.29e12
 SHAPES = [(m, 200000, 768, 10) for m in (1, 4, 16)] + [(16, 200000, 768, 128)] + [(m, 18000, 384, 10) for m in (1, 4, 16)]
 
 
-def timed(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), out
-
-
-def stats(v):
-    return {"median_ms": round(float(np.median(v)), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    assert torch.cuda.is_available(), "needs the GPU"
-    lib = cva.lib.load()
-    res = {"device": torch.cuda.get_device_name(0), "calls": args.calls, "warmup": args.warmup, "timer": "HIP events around one call, arms alternating",
-           "hbm_stream_tb_per_s": HBM_STREAM_BYTES_PER_S / 1e12, "shapes": []}
+    args, lib, res = start(hbm_stream_tb_per_s=HBM_STREAM_BYTES_PER_S / 1e12, shapes=[])
     made = {}
     for m, n, d, k in SHAPES:
         if (n, d) not in made:
@@ -61,17 +35,11 @@ def main():
                 "b_gallery_index_search": lambda: index.search(q, k)[:2],
                 "a2_retrieval_topk_device": lambda: retrieval_topk_device(q, g, k, normalize=True)[:2],
                 "c_torch_matmul_topk": lambda: torch.topk(q_unit @ g_unit.T, k)}
-        ms = {a: [] for a in arms}
-        for it in range(args.warmup + args.calls):
-            for a, fn in arms.items():
-                t, out = timed(fn)
-                if it >= args.warmup:
-                    ms[a].append(t)
+        ms = alternate(arms, list(arms), args.calls, args.warmup)
         want, got = arms["a1_retrieval_topk_device"](), arms["b_gallery_index_search"]()
         torch.cuda.synchronize()
-        same = bool((want[0] == got[0]).all()) and bool((want[1].view(torch.int32) == got[1].view(torch.int32)).all())
         row = {"M": m, "N": n, "d": d, "K": k, "workspace_bytes": int(lib.coot_retrieval_topk_few_workspace_bytes(m, n, d, k)),
-               "gallery_bytes": n * d * 4, "same_bytes_as_retrieval_topk_device": same}
+               "gallery_bytes": n * d * 4, "same_bytes_as_retrieval_topk_device": same(want, got)}
         for a, v in ms.items():
             row[a] = stats(v)
         a1, a2, b = (row[x]["median_ms"] for x in ("a1_retrieval_topk_device", "a2_retrieval_topk_device", "b_gallery_index_search"))
@@ -82,10 +50,7 @@ def main():
                     "hbm_floor_ms": round(floor, 4), "b_over_hbm_floor": round(b / floor, 2)})
         res["shapes"].append(row)
         print(json.dumps(row), flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)) or ".", exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
+    finish(args, res)
 
 
 if __name__ == "__main__":

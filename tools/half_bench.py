@@ -8,15 +8,10 @@ the same rows (the fp32 one the unrounded ones).  hbm_floor_ms = the bytes of on
 the 16-bit gallery; the small gallery fits the caches, so its floors are reported but prove nothing.  An arm counts as faster only
 when it beats min(a1, a2) by more than (a)'s spread = |median a1 - median a2| and than its min-max range.
 Usage: python tools/half_bench.py [--calls 20] [--warmup 5] [--out profiles/<tag>_topk_half.json]"""
-import argparse
 import json
-import os
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
+from _retrieval_bench import alternate, finish, same, start, stats
 import torch
-import coot_videotext_amd as cva
 from coot_videotext_amd.retrieval import GalleryIndex, retrieval_topk_device
 
 HBM_STREAM_BYTES_PER_S = 6.29e12
@@ -24,33 +19,8 @@ SHAPES = [(m, 200000, 768, 10) for m in (1, 4, 16)] + [(16, 200000, 768, 128)] +
 ARMS = ("a1_fp32_index", "b_bf16_index", "c_half_index", "a2_fp32_index")
 
 
-def timed(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), out
-
-
-def stats(v):
-    return {"median_ms": round(float(np.median(v)), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
-
-
-def same(x, y):
-    return bool((x[0] == y[0]).all()) and bool((x[1].view(torch.int32) == y[1].view(torch.int32)).all())
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    assert torch.cuda.is_available(), "needs the GPU"
-    cva.lib.load()
-    res = {"device": torch.cuda.get_device_name(0), "library": os.path.basename(cva.lib.LIB_PATH), "calls": args.calls, "warmup": args.warmup,
-           "timer": "HIP events around one call, arms alternating", "hbm_stream_tb_per_s": HBM_STREAM_BYTES_PER_S / 1e12, "shapes": []}
+    args, _, res = start(library=True, hbm_stream_tb_per_s=HBM_STREAM_BYTES_PER_S / 1e12, shapes=[])
     made = {}
     for m, n, d, k in SHAPES:
         if (n, d) not in made:
@@ -63,12 +33,7 @@ def main():
         q = torch.randn(m, d, device="cuda", generator=gen) + 0.35 * g[torch.arange(m, device="cuda") * 7 % n]
         arms = {"a1_fp32_index": lambda: i32.search(q, k)[:2], "b_bf16_index": lambda: ibf.search(q, k)[:2],
                 "c_half_index": lambda: ihf.search(q, k)[:2], "a2_fp32_index": lambda: i32.search(q, k)[:2]}
-        ms = {a: [] for a in ARMS}
-        for it in range(args.warmup + args.calls):
-            for a in ARMS:
-                t, out = timed(arms[a])
-                if it >= args.warmup:
-                    ms[a].append(t)
+        ms = alternate(arms, ARMS, args.calls, args.warmup)
         # the definition, once per shape: the 16-bit index returns the bytes of the fp32 tile call on the widened gallery
         ok = {}
         for name, idx in (("bf16", ibf), ("half", ihf)):
@@ -93,10 +58,7 @@ def main():
                     "half_over_its_floor": round(c / floor16, 2)})
         res["shapes"].append(row)
         print(json.dumps(row), flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)) or ".", exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
+    finish(args, res)
 
 
 if __name__ == "__main__":

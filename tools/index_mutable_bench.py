@@ -22,43 +22,17 @@ Per (gallery, storage):
             spread = |median f1 - median f2| + (max - min over f1 and f2), and the results are checked to be the same bytes.
 The timer brackets the whole Python call, allocation included: what a caller waits for on an otherwise idle stream.
 Usage: python tools/index_mutable_bench.py [--calls 20] [--warmup 5] [--out profiles/<tag>_index_mutable.json]"""
-import argparse
 import json
-import os
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _retrieval_bench import alternate as run, finish, same, spread, start, stats
 import numpy as np
 import torch
-import coot_videotext_amd as cva
 from coot_videotext_amd.retrieval import GalleryIndex
 
 GALLERIES = [(200000, 768), (18000, 384)]
 STORAGES = ("float32", "bfloat16")
 QUERIES = (1, 16)
 K = 10
-
-
-def timed(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), out
-
-
-def stats(v):
-    return {"median_ms": round(float(np.median(v)), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
-
-
-def spread(v1, v2):
-    """The run-to-run spread of an arm timed twice: the gap between its two medians plus its min-max range."""
-    return abs(float(np.median(v1)) - float(np.median(v2))) + (max(v1 + v2) - min(v1 + v2))
-
-
-def same(x, y):
-    return bool((x[0] == y[0]).all()) and bool((x[1].view(torch.int32) == y[1].view(torch.int32)).all())
 
 
 def same_index(a, b):
@@ -68,32 +42,10 @@ def same_index(a, b):
             and bool((a.norms.view(torch.int32) == b.norms.view(torch.int32)).all()))
 
 
-def run(arms, order, calls, warmup):
-    """arms: name -> (setup or None, call); setup runs untimed before each call and its result is passed to the call."""
-    ms = {a: [] for a in order}
-    for it in range(warmup + calls):
-        for a in order:
-            setup, call = arms[a]
-            arg = setup() if setup else None
-            t, _ = timed((lambda: call(arg)) if setup else call)
-            if it >= warmup:
-                ms[a].append(t)
-            del arg
-    return ms
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    assert torch.cuda.is_available(), "needs the GPU"
-    cva.lib.load()
+    args, _, res = start(timer="HIP events around one Python call (allocation included), arms alternating", library=True, K=K,
+                         spread="|median of the first timing - median of the second| + (max - min over both)", changes=[], compact=[], search=[])
     rounds = args.calls + args.warmup
-    res = {"device": torch.cuda.get_device_name(0), "library": os.path.basename(cva.lib.LIB_PATH), "calls": args.calls, "warmup": args.warmup,
-           "timer": "HIP events around one Python call (allocation included), arms alternating", "K": K,
-           "spread": "|median of the first timing - median of the second| + (max - min over both)", "changes": [], "compact": [], "search": []}
     for n, d in GALLERIES:
         torch.cuda.empty_cache()
         gen = torch.Generator(device="cuda").manual_seed(n + d)
@@ -174,10 +126,7 @@ def main():
                 res["search"].append(row)
                 print(json.dumps(row), flush=True)
             del grown, fresh, stored
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)) or ".", exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
+    finish(args, res)
 
 
 if __name__ == "__main__":

@@ -5,39 +5,17 @@ labels = arange, at the ActivityNet validation shape (4 917 x 4 917 x 768), norm
 alternating call by call in one process; medians.  The square arm is timed twice per round: the difference of its two medians is
 the run-to-run spread the labelled call is read against.
 Usage: python tools/labeled_bench.py [--calls 20] [--warmup 5] [--out profiles/<tag>_labeled.json]"""
-import argparse
 import json
-import os
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
+from _retrieval_bench import alternate, finish, start, stats
 import torch
-import coot_videotext_amd as cva
 from coot_videotext_amd.retrieval import retrieval_ranks_device, retrieval_ranks_labeled_device
 
 SHAPES = ((4917, 4917, 768), (20000, 4917, 768))
 
 
-def timed(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), out
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    assert torch.cuda.is_available(), "needs the GPU"
-    lib = cva.lib.load()
-    res = {"device": torch.cuda.get_device_name(0), "calls": args.calls, "warmup": args.warmup, "timer": "HIP events around one call, arms alternating",
-           "normalize": True, "shapes": []}
+    args, lib, res = start(normalize=True, shapes=[])
     for m, n, d in SHAPES:
         gen = torch.Generator(device="cuda").manual_seed(m + n)
         g = torch.randn(n, d, device="cuda", generator=gen)
@@ -47,12 +25,7 @@ def main():
         if m == n:
             arms = {"coot_retrieval_ranks": lambda: retrieval_ranks_device(q, g, normalize=True), **arms,
                     "coot_retrieval_ranks_again": lambda: retrieval_ranks_device(q, g, normalize=True)}
-        ms = {a: [] for a in arms}
-        for it in range(args.warmup + args.calls):
-            for a, fn in arms.items():
-                t, out = timed(fn)
-                if it >= args.warmup:
-                    ms[a].append(t)
+        ms = alternate(arms, list(arms), args.calls, args.warmup)
         row = {"M": m, "N": n, "d": d, "queries_per_item": round(m / n, 2),
                "workspace_bytes": int(lib.coot_retrieval_ranks_labeled_workspace_bytes(m, n, d)), "matrix_bytes": m * n * 4}
         rq, rg, nv, met, _ = arms["coot_retrieval_ranks_labeled"]()
@@ -62,7 +35,7 @@ def main():
             r12, r21, met_r, _ = arms["coot_retrieval_ranks"]()
             row["equals_the_square_call"] = bool(torch.equal(rq, r12) and torch.equal(rg, r21) and torch.equal(met, met_r))
         for a, v in ms.items():
-            row[a] = {"median_ms": round(float(np.median(v)), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
+            row[a] = stats(v)
         if m == n:
             sq = [row["coot_retrieval_ranks"]["median_ms"], row["coot_retrieval_ranks_again"]["median_ms"]]
             row["square_run_to_run_ms"] = round(abs(sq[0] - sq[1]), 4)
@@ -71,10 +44,7 @@ def main():
         print(json.dumps(row), flush=True)
         del q, g
         torch.cuda.empty_cache()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)) or ".", exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
+    finish(args, res)
 
 
 if __name__ == "__main__":

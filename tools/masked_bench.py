@@ -15,13 +15,10 @@ Arms:
 An arm counts as faster than the unfiltered search only when it beats min(a1, a2) by more than (a)'s spread, defined as above.
 Every filtered arm is checked once per shape against its definition (the unfiltered search on gallery[keep], indices mapped back).
 Usage: python tools/masked_bench.py [--calls 20] [--warmup 5] [--parent-lib path/libcoot_hip.so] [--out profiles/<tag>_topk_masked.json]"""
-import argparse
 import ctypes
 import json
-import os
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _retrieval_bench import alternate, finish, same, spread, start, stats
 import numpy as np
 import torch
 import coot_videotext_amd as cva
@@ -31,37 +28,15 @@ GALLERIES = [(200000, 768), (18000, 384)]
 QUERIES = (1, 16, 1024)
 K = 10
 STORAGES = ("float32", "bfloat16")
-UNMASKED_CALLS = ("coot_retrieval_topk_workspace_bytes", "coot_retrieval_topk", "coot_retrieval_topk_few_workspace_bytes", "coot_retrieval_topk_few",
-                  "coot_retrieval_topk_few_h")
-
-
-def timed(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), out
-
-
-def stats(v):
-    return {"median_ms": round(float(np.median(v)), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
-
-
-def spread(v1, v2):
-    """The run-to-run spread of an arm timed twice: the gap between its two medians plus its min-max range."""
-    return abs(float(np.median(v1)) - float(np.median(v2))) + (max(v1 + v2) - min(v1 + v2))
-
-
-def same(x, y):
-    return bool((x[0] == y[0]).all()) and bool((x[1].view(torch.int32) == y[1].view(torch.int32)).all())
+SEARCH_CALLS = ("coot_retrieval_topk_workspace_bytes", "coot_retrieval_topk_masked", "coot_retrieval_topk_few_workspace_bytes",
+                "coot_retrieval_topk_few_masked")  # what an unfiltered search calls (keep = NULL)
 
 
 def other_build(path):
-    """Another build of the library with the unmasked search calls bound as lib.load() binds them."""
+    """Another build of the library with the search calls bound as lib.load() binds them."""
     here = cva.lib.load()
     lib = ctypes.CDLL(path)
-    for name in UNMASKED_CALLS:
+    for name in SEARCH_CALLS:
         getattr(lib, name).argtypes = getattr(here, name).argtypes
         getattr(lib, name).restype = getattr(here, name).restype
     return lib
@@ -87,18 +62,10 @@ def definition(index, q, keep):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--parent-lib", default=None)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    assert torch.cuda.is_available(), "needs the GPU"
-    cva.lib.load()
+    args, _, res = start(timer="HIP events around one GalleryIndex.search call, arms alternating", library=True, options=["--parent-lib"], K=K,
+                         spread="|median of the first timing - median of the second| + (max - min over both)", shapes=[])
     parent = other_build(args.parent_lib) if args.parent_lib else None
-    res = {"device": torch.cuda.get_device_name(0), "library": os.path.basename(cva.lib.LIB_PATH), "parent_library_timed": parent is not None,
-           "calls": args.calls, "warmup": args.warmup, "timer": "HIP events around one GalleryIndex.search call, arms alternating", "K": K,
-           "spread": "|median of the first timing - median of the second| + (max - min over both)", "shapes": []}
+    res["parent_library_timed"] = parent is not None
     for n, d in GALLERIES:
         torch.cuda.empty_cache()
         gen = torch.Generator(device="cuda").manual_seed(n + d)
@@ -118,12 +85,7 @@ def main():
                 if parent is not None:
                     arms["p1"] = arms["p2"] = through(parent, plain)
                     order = ["p1"] + order + ["p2"]
-                ms = {a: [] for a in order}
-                for it in range(args.warmup + args.calls):
-                    for a in order:
-                        t, out = timed(arms[a])
-                        if it >= args.warmup:
-                            ms[a].append(t)
+                ms = alternate(arms, order, args.calls, args.warmup)
                 row = {"M": m, "N": n, "d": d, "storage": storage, "kept": {k: int(v.sum()) for k, v in keeps.items()}}
                 row["same_bytes_as_the_unfiltered_search_on_the_compacted_gallery"] = {k: same(arms[k](), definition(index, q, v)) for k, v in keeps.items()}
                 if parent is not None:
@@ -144,10 +106,7 @@ def main():
                 res["shapes"].append(row)
                 print(json.dumps(row), flush=True)
             del index
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)) or ".", exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
+    finish(args, res)
 
 
 if __name__ == "__main__":

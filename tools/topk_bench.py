@@ -4,40 +4,19 @@ on the same device, at the ActivityNet validation shape (4 917 x 4 917 x 768), t
 1 024 queries x 200 000 clips x 768, K = 10.  HIP events around single calls, the two arms alternating call by call on one box;
 medians.  FLOPs = 2 M N d (the similarities; the selection is not counted), share of the fp32 vector peak (157.3 TFLOP/s).
 Usage: python tools/topk_bench.py [--calls 20] [--warmup 5] [--out profiles/<tag>_topk.json]"""
-import argparse
 import json
-import os
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _retrieval_bench import alternate, finish, start
 import numpy as np
 import torch
-import coot_videotext_amd as cva
 from coot_videotext_amd.retrieval import retrieval_topk_device
 
 PEAK_FP32_VALU = 157.3e12
 SHAPES = ((4917, 4917, 768, 10), (18000, 18000, 384, 10), (1024, 200000, 768, 10))
 
 
-def timed(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), out
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    assert torch.cuda.is_available(), "needs the GPU"
-    lib = cva.lib.load()
-    res = {"device": torch.cuda.get_device_name(0), "calls": args.calls, "warmup": args.warmup, "timer": "HIP events around one call, arms alternating",
-           "peak_fp32_valu_tflops": PEAK_FP32_VALU / 1e12, "shapes": []}
+    args, lib, res = start(peak_fp32_valu_tflops=PEAK_FP32_VALU / 1e12, shapes=[])
     for m, n, d, k in SHAPES:
         gen = torch.Generator(device="cuda").manual_seed(m + n)
         g = torch.randn(n, d, device="cuda", generator=gen)
@@ -47,12 +26,7 @@ def main():
         arms = {"coot_retrieval_topk": lambda: retrieval_topk_device(q, g, k)[:2],
                 "coot_retrieval_topk_normalize": lambda: retrieval_topk_device(q, g, k, normalize=True)[:2],
                 "torch_matmul_topk": lambda: torch.topk(q @ g.T, k)}
-        ms = {a: [] for a in arms}
-        for it in range(args.warmup + args.calls):
-            for a, fn in arms.items():
-                t, out = timed(fn)
-                if it >= args.warmup:
-                    ms[a].append(t)
+        ms = alternate(arms, list(arms), args.calls, args.warmup)
         idx, sc = arms["coot_retrieval_topk"]()
         tv, ti = arms["torch_matmul_topk"]()
         torch.cuda.synchronize()
@@ -69,10 +43,7 @@ def main():
         print(json.dumps(row), flush=True)
         del q, g
         torch.cuda.empty_cache()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)) or ".", exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
+    finish(args, res)
 
 
 if __name__ == "__main__":
