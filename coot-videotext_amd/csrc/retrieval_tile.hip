@@ -39,9 +39,11 @@ __global__ __launch_bounds__(256) void rt_normalize_kernel(const float* a, const
 // acc[r][c] accumulates in k order, chunk by chunk: the same chain for every element in every pass.
 // A has NA rows, B has NB rows.  NORM (the top-K search, which keeps no normalised copy of a 200 000-row gallery): the staged value
 // is x / norm of its row, the division rt_normalize_kernel makes, so the chain sees the same operands as on a normalised copy.
+// TB (the search on a prepared gallery, which may hold 16-bit rows): the element type of B, widened as it is staged; from LDS on
+// nothing knows of it.
 struct Tile { float acc[4][4]; };
-template <bool NORM = false>
-__device__ __forceinline__ void tile_dot(const float* A, const float* B, int NA, int NB, int d, int i0, int j0, float (*As)[RP], float (*Bs)[RP], Tile& t,
+template <bool NORM = false, typename TB = float>
+__device__ __forceinline__ void tile_dot(const float* A, const TB* B, int NA, int NB, int d, int i0, int j0, float (*As)[RP], float (*Bs)[RP], Tile& t,
                                          const float* nA = nullptr, const float* nB = nullptr) {
   const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
   float ra[8], rb[8];  // NORM: the norms of the 8 rows of each operand this thread stages (the same rows in every chunk)
@@ -65,10 +67,10 @@ __device__ __forceinline__ void tile_dot(const float* A, const float* B, int NA,
       const bool kin = k0 + k < d;
       if (NORM) {
         As[r][k] = (kin && i0 + r < NA) ? A[(long)(i0 + r) * d + k0 + k] / ra[q] : 0.f;
-        Bs[r][k] = (kin && j0 + r < NB) ? B[(long)(j0 + r) * d + k0 + k] / rb[q] : 0.f;
+        Bs[r][k] = (kin && j0 + r < NB) ? widen(B[(long)(j0 + r) * d + k0 + k]) / rb[q] : 0.f;
       } else {
         As[r][k] = (kin && i0 + r < NA) ? A[(long)(i0 + r) * d + k0 + k] : 0.f;
-        Bs[r][k] = (kin && j0 + r < NB) ? B[(long)(j0 + r) * d + k0 + k] : 0.f;
+        Bs[r][k] = (kin && j0 + r < NB) ? widen(B[(long)(j0 + r) * d + k0 + k]) : 0.f;
       }
     }
     __syncthreads();
@@ -334,6 +336,81 @@ __global__ __launch_bounds__(256) void rt_topk_kernel(const float* A, const floa
   }
 }
 
+// rt_topk_kernel on the 16-bit rows of a prepared gallery (coot_retrieval_topk_index; TB = unsigned short: bfloat16, or _Float16): the
+// same statements, B of element type TB, which tile_dot widens as it stages it; nB are the norms the caller holds.  A kernel of its
+// own and not a body shared with rt_topk_kernel: moved into a function that both kernels inline, the four fp32 instantiations come out
+// with another instruction schedule (tools/kernel_isa.py), and they are promised to stay the parent's instruction for instruction.
+template <typename TB, bool NORM, bool MASKED>
+__global__ __launch_bounds__(256) void rt_topk_index_kernel(const float* A, const TB* B, const float* nA, const float* nB, int M, int N, int d,
+                                                            int K, int tiles_per_split, int S, float* sim, tk_entry_t* part, int* idx_out,
+                                                            float* score_out, const unsigned char* keep) {
+  extern __shared__ __attribute__((aligned(16))) char tk_lds[];
+  float (*As)[RP] = (float (*)[RP])tk_lds;
+  float (*Bs)[RP] = (float (*)[RP])(tk_lds + RT * RP * 4);
+  tk_entry_t* cand = (tk_entry_t*)(tk_lds + 2 * RT * RP * 4);
+  tk_entry_t* list = cand + RT * RT;
+  int* cnt = (int*)(list + RT * K);
+  int* ncand = cnt + RT;
+  const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15, wave = tid >> 6, lane = tid & 63;
+  const int i0 = blockIdx.y * RT, nt = (N + RT - 1) / RT;
+  const int t0 = blockIdx.x * tiles_per_split, t1 = min(nt, t0 + tiles_per_split);
+  if (tid < RT) { cnt[tid] = 0; ncand[tid] = 0; }
+  for (int e = tid; e < RT * K; e += 256) list[e] = 0ull;  // 0 = behind every entry: an unfilled slot
+  for (int tj = t0; tj < t1; ++tj) {
+    const int j0 = tj * RT;
+    unsigned kp = 0u;  // MASKED: bit c = the keep flag of column j0 + 4 tx + c
+    if constexpr (MASKED) {
+      if (!sim && !__syncthreads_or(tid < RT && j0 + tid < N && keep[j0 + tid])) continue;  // (uniform: nothing of this tile is touched)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) kp |= (j0 + 4 * tx + c < N && keep[j0 + 4 * tx + c]) ? 1u << c : 0u;
+    }
+    Tile t;
+    tile_dot<NORM, TB>(A, B, M, N, d, i0, j0, As, Bs, t, nA, nB);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = 4 * ty + r, i = i0 + row;
+      if (i >= M) continue;
+      const bool full = cnt[row] >= K;
+      const tk_entry_t kth = list[row * K + K - 1];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int j = j0 + 4 * tx + c;
+        if (j >= N) continue;
+        const float s = t.acc[r][c];
+        if (sim) sim[(long)i * N + j] = s;
+        if constexpr (MASKED) { if (!(kp >> c & 1u)) continue; }
+        const tk_entry_t e = tk_pack(s, j);
+        if (!full || e > kth) cand[row * RT + atomicAdd(&ncand[row], 1)] = e;  // <= RT columns of this tile per row
+      }
+    }
+    __syncthreads();
+    for (int row = wave; row < RT; row += 4) {
+      const int nc = ncand[row], n = cnt[row];
+      tk_entry_t* L = list + row * K;
+      const tk_entry_t* C = cand + row * RT;
+      TkFold f;
+      f.read(L, n, C, nc, lane);
+      __syncthreads();
+      if (nc) {
+        f.place(L, K);
+        if (lane == 0) { cnt[row] = min(K, n + nc); ncand[row] = 0; }
+      }
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < RT * K; e += 256) {
+    const int row = e / K, r = e - row * K, i = i0 + row;
+    if (i >= M) continue;
+    const tk_entry_t v = list[e];
+    if (S == 1) {
+      idx_out[(long)i * K + r] = MASKED ? tk_idx_masked(v) : (int)(unsigned)v;
+      score_out[(long)i * K + r] = MASKED ? tk_score_masked(v) : tk_score(v);
+    } else {
+      part[((long)i * S + blockIdx.x) * K + r] = v;
+    }
+  }
+}
+
 // one wave per row: part [M][S][K], every list sorted best first, unfilled slots 0 at its end
 // MASKED: the real entries of a row may total R < K (a split whose columns are all masked hands in an all-unfilled list).  A real
 // entry's rank is its position among the real ones, below R.  An unfilled slot at position p of list s, which holds n_s real
@@ -376,6 +453,32 @@ TkWs tk_layout(void* base, int M, int N, int K, int S) {
   return w;
 }
 
+// The tile kernel on a gallery of element type T and, with more than one split, the merge: what every tile search launches after its
+// norms.  fp32 rows take rt_topk_kernel, 16-bit rows rt_topk_index_kernel; na / nb == nullptr: the instantiations without NORM.
+template <typename T>
+int tk_launch(const float* queries, const T* gallery, const float* na, const float* nb, const unsigned char* keep, int M, int N, int d, int K, TkSplit sp,
+              tk_entry_t* part, int32_t* idx_out, float* score_out, float* sim_out, hipStream_t st) {
+  with_bool(na != nullptr, keep != nullptr, [&](auto norm, auto masked) {
+    constexpr bool NORM = decltype(norm)::value, MASKED = decltype(masked)::value;
+    const dim3 grid(sp.S, (M + RT - 1) / RT);
+    if constexpr (std::is_same_v<T, float>)
+      hipLaunchKernelGGL((rt_topk_kernel<NORM, MASKED>), grid, dim3(256), tk_lds_bytes(K), st, queries, gallery, na, nb, M, N, d, K, sp.tiles, sp.S, sim_out,
+                         part, (int*)idx_out, score_out, keep);
+    else
+      hipLaunchKernelGGL((rt_topk_index_kernel<T, NORM, MASKED>), grid, dim3(256), tk_lds_bytes(K), st, queries, gallery, na, nb, M, N, d, K, sp.tiles, sp.S,
+                         sim_out, part, (int*)idx_out, score_out, keep);
+  });
+  COOT_CHECK_LAUNCH("rt_topk");
+  if (sp.S > 1) {
+    with_bool(keep != nullptr, [&](auto masked) {
+      hipLaunchKernelGGL(rt_topk_merge_kernel<decltype(masked)::value>, dim3((M + 3) / 4), dim3(256), 0, st, (const tk_entry_t*)part, M, sp.S, K,
+                         (int*)idx_out, score_out);
+    });
+    COOT_CHECK_LAUNCH("rt_topk_merge");
+  }
+  return 0;
+}
+
 // coot_retrieval_topk and coot_retrieval_topk_masked (keep == nullptr: the unmasked kernels, launched as coot_retrieval_topk
 // launches them): fn names the entry in a refusal
 int topk_search(const char* fn, const float* queries, const float* gallery, const unsigned char* keep, int M, int N, int d, int K, int normalize,
@@ -390,20 +493,18 @@ int topk_search(const char* fn, const float* queries, const float* gallery, cons
     rt_launch_norms(queries, M, gallery, N, d, w.na, w.nb, st);
     COOT_CHECK_LAUNCH("rt_norms");
   }
-  const float *na = normalize ? w.na : nullptr, *nb = normalize ? w.nb : nullptr;  // the instantiations without NORM get no norms
-  with_bool(normalize, keep != nullptr, [&](auto norm, auto masked) {
-    hipLaunchKernelGGL((rt_topk_kernel<decltype(norm)::value, decltype(masked)::value>), dim3(sp.S, (M + RT - 1) / RT), dim3(256), tk_lds_bytes(K), st,
-                       queries, gallery, na, nb, M, N, d, K, sp.tiles, sp.S, sim_out, w.part, (int*)idx_out, score_out, keep);
-  });
-  COOT_CHECK_LAUNCH("rt_topk");
-  if (sp.S > 1) {
-    with_bool(keep != nullptr, [&](auto masked) {
-      hipLaunchKernelGGL(rt_topk_merge_kernel<decltype(masked)::value>, dim3((M + 3) / 4), dim3(256), 0, st, (const tk_entry_t*)w.part, M, sp.S, K,
-                         (int*)idx_out, score_out);
-    });
-    COOT_CHECK_LAUNCH("rt_topk_merge");
-  }
-  return 0;
+  // the instantiations without NORM get no norms
+  return tk_launch(queries, gallery, normalize ? w.na : nullptr, normalize ? w.nb : nullptr, keep, M, N, d, K, sp, w.part, idx_out, score_out, sim_out, st);
+}
+
+// coot_retrieval_topk_index: the query norms and the partial lists; the gallery's norms are the caller's
+struct TkIndexWs { float* na; tk_entry_t* part; size_t bytes; };
+TkIndexWs tk_index_layout(void* base, int M, int K, int S) {
+  Arena a{(char*)base}; TkIndexWs w;
+  w.na = a.take<float>(M);
+  w.part = a.take<tk_entry_t>(S > 1 ? (size_t)M * S * K : 0);
+  w.bytes = a.off;
+  return w;
 }
 
 // ---- labelled ranking: M queries, N gallery rows, labels[i] = the gallery row of query i (coot_retrieval_ranks_labeled) ------
@@ -642,6 +743,36 @@ int coot_retrieval_topk_masked(const float* queries, const float* gallery, const
                                int32_t* idx_out, float* score_out, float* sim_out, void* workspace, size_t workspace_bytes, coot_stream_t stream) {
   return topk_search("retrieval_topk_masked", queries, gallery, keep, M, N, d, K, normalize, idx_out, score_out, sim_out, workspace, workspace_bytes,
                      (hipStream_t)stream);
+}
+
+size_t coot_retrieval_topk_index_workspace_bytes(int M, int N, int d, int K) {
+  (void)d;
+  if (M < 1 || N < 1 || K < 1) return 0;
+  return tk_index_layout(nullptr, M, K, tk_split(M, N).S).bytes;  // exact: the call refuses one byte less
+}
+
+int coot_retrieval_topk_index(const float* queries, const void* gallery, int gallery_dtype, const float* gallery_norms, const uint8_t* keep, int M, int N,
+                              int d, int K, int32_t* idx_out, float* score_out, float* sim_out, void* workspace, size_t workspace_bytes,
+                              coot_stream_t stream) {
+  const char* fn = "retrieval_topk_index";
+  COOT_REQUIRE(gallery_dtype == COOT_GALLERY_F32 || gallery_dtype == COOT_GALLERY_BF16 || gallery_dtype == COOT_GALLERY_F16,
+               "%s: gallery_dtype = %d (COOT_GALLERY_F32, COOT_GALLERY_BF16 or COOT_GALLERY_F16)", fn, gallery_dtype);
+  COOT_REQUIRE(queries && gallery && idx_out && score_out && workspace, "%s: null pointer", fn);
+  COOT_REQUIRE(M >= 1 && N >= 1 && d >= 1 && (M + RT - 1) / RT <= 65535, "%s: M = %d, N = %d, d = %d", fn, M, N, d);
+  COOT_REQUIRE(K >= 1 && K <= N && K <= TK_MAX, "%s: K = %d is outside 1 .. min(N = %d, %d)", fn, K, N, TK_MAX);
+  COOT_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace is not 8-byte aligned", fn);
+  hipStream_t st = (hipStream_t)stream;
+  const TkSplit sp = tk_split(M, N);
+  TkIndexWs w = tk_index_layout(workspace, M, K, sp.S);
+  COOT_REQUIRE(w.bytes <= workspace_bytes, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, w.bytes);
+  if (gallery_norms) {  // the queries' norms only: one launch over M rows
+    rt_launch_norms(queries, M, nullptr, 0, d, w.na, nullptr, st);
+    COOT_CHECK_LAUNCH("rt_norms");
+  }
+  return with_elem(gallery_dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return tk_launch(queries, (const T*)gallery, gallery_norms ? w.na : nullptr, gallery_norms, keep, M, N, d, K, sp, w.part, idx_out, score_out, sim_out, st);
+  });
 }
 
 size_t coot_retrieval_ranks_labeled_workspace_bytes(int M, int N, int d) {

@@ -8,14 +8,15 @@ in four launches, the N x N matrix is never materialised).  No CPU 
 
 compute_retrieval_topk / retrieval_topk_device: WHICH gallery items a query retrieves (the reference returns top1 only), for M
 queries against N gallery rows, M and N independent: the host mirror on a similarity matrix, and the tile search on the device
-(similarities and selection fused, no M x N matrix).  GalleryIndex: the same search for a few queries at a time on a gallery that
-stays on the device, its row norms computed once (the few-query search: the same bytes, one sweep of the gallery); the gallery may
-be held in bfloat16 or float16 (the bytes of the search on the gallery widened to fp32).
+(similarities and selection fused, no M x N matrix).  GalleryIndex: the same search on a gallery that stays on the device, its row
+norms computed once: a few queries at a time (the few-query search: the same bytes, one sweep of the gallery) or a whole query set
+(retrieval_topk_index_device: the tile search on the gallery as the index holds it, with the norms it has); the gallery may be held
+in bfloat16 or float16 (the bytes of the search on the gallery widened to fp32).
 Filtered search (compute_retrieval_topk_masked; keep= of retrieval_topk_device and GalleryIndex.search; GalleryIndex.remove /
 restore): a keep flag per gallery row that the selection consults — the bytes of the unfiltered search on gallery[keep] with its
-indices mapped back, without the copy.  Each search is one library call whatever the arguments: coot_retrieval_topk_masked (tile) and
-coot_retrieval_topk_few_masked (few queries, any storage), which with keep = NULL launch what coot_retrieval_topk,
-coot_retrieval_topk_few and coot_retrieval_topk_few_h launch.
+indices mapped back, without the copy.  Each search is one library call whatever the arguments: coot_retrieval_topk_masked (tile),
+coot_retrieval_topk_index (tile, on an index) and coot_retrieval_topk_few_masked (few queries, any storage), which with keep = NULL
+launch what coot_retrieval_topk, coot_retrieval_topk_few and coot_retrieval_topk_few_h launch.
 A gallery that changes (GalleryIndex.add / update / compact): rows appended into spare capacity or overwritten in place together with
 their norms (coot_retrieval_rows_put: O(R d) bytes, no synchronisation), removed rows dropped physically — after any sequence of
 them the index holds, byte for byte, what a fresh index on the same rows holds.
@@ -169,6 +170,52 @@ def _gallery_codes():
     return {torch.float32: 0, torch.bfloat16: GALLERY_BF16, torch.float16: GALLERY_F16}
 
 
+# GalleryIndex.search on a 16-bit index: from this many queries on, one tile call (coot_retrieval_topk_index); below it, slices of
+# RETRIEVAL_FEW_MAX queries through the few-query call, one sweep of the gallery each.  The tile walk runs at most 64 workgroups per 64
+# queries, so up to 256 queries it takes about as long as for 17 (5.9 - 7.7 ms at 200 000 x 768, where a sweep takes 0.3 - 0.45 ms).
+# The smallest measured M from which the tile call is no slower than the slices at both measured galleries (profiles/r17_topk_index.json:
+# M = 17, 32, 64, 256, 320, 512, 1 024): at 200 000 x 768 it loses up to and including 256 queries (6.94 against 6.79 ms, more than the
+# slices' spread) and wins from 320 (6.94 against 9.19); at 18 000 x 384 it already wins from 64 filtered and 256 unfiltered (0.75
+# against 2.62 ms), which this one threshold leaves to the slices.  A float32 index takes the tile call from 17 queries on: there the
+# alternative was the same walk plus a pass over the gallery for its norms.
+INDEX_TILE_MIN_M_16BIT = 320
+
+
+def retrieval_topk_index_device(queries, gallery, norms, k: int, keep=None, want_sim: bool = False):
+    """The tile search on a gallery as a prepared index holds it (coot_retrieval_topk_index): queries cuda float32 [M, d], gallery
+    cuda float32, bfloat16 or float16 [N, d], norms cuda float32 [N] = the gallery's row norms as coot_retrieval_row_norms(_h)
+    writes them (GalleryIndex.norms), or None: rows used as they are.  Returns (idx int32 [M, k], scores float32 [M, k], sim [M, N] or
+    None) on the device, no synchronisation: the bytes of retrieval_topk_device(queries, gallery.float(), k, normalize=norms is not
+    None, keep=keep), without the widened copy and without a pass over the gallery for its norms — they are read, not checked.
+    Any M >= 1, 1 <= k <= min(N, 128); keep as in retrieval_topk_device."""
+    import torch
+    from . import lib as _lib
+    fn = "retrieval_topk_index_device"
+    if keep is not None:
+        assert gallery.dim() == 2, gallery.shape
+        keep = _check_keep(fn, keep, gallery.shape[0])
+    if not (queries.is_cuda and gallery.is_cuda and (norms is None or norms.is_cuda)):
+        raise RuntimeError(f"{fn} needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk" + ("_masked)" if keep is not None else ")"))
+    codes = _gallery_codes()
+    if gallery.dtype not in codes:
+        raise ValueError(f"{fn}: a gallery of dtype {gallery.dtype}; it has to be {_STORAGE_NAMES}")
+    assert queries.dtype == torch.float32 and queries.dim() == 2 and gallery.dim() == 2, (queries.dtype, queries.shape, gallery.shape)
+    (m, d), n, k = queries.shape, gallery.shape[0], int(k)
+    if gallery.shape[1] != d:
+        raise ValueError(f"{fn}: queries of width {d}, gallery of width {gallery.shape[1]}")
+    if not 1 <= k <= min(n, 128):
+        raise ValueError(f"{fn}: k = {k} is outside 1 .. min(N = {n}, 128)")
+    assert norms is None or (norms.dtype == torch.float32 and tuple(norms.shape) == (n,)), (norms.dtype, norms.shape, n)
+    queries, gallery, norms = queries.contiguous(), gallery.contiguous(), None if norms is None else norms.contiguous()
+    lib = _lib.load()
+    ws, idx, scores, sim = _topk_buffers(lib.coot_retrieval_topk_index_workspace_bytes(m, n, d, k), m, n, k, want_sim, queries.device)
+    _lib.check(lib.coot_retrieval_topk_index(queries.data_ptr(), gallery.data_ptr(), codes[gallery.dtype], None if norms is None else norms.data_ptr(),
+                                             None if keep is None else keep.data_ptr(), m, n, d, k, idx.data_ptr(), scores.data_ptr(),
+                                             sim.data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
+               "coot_retrieval_topk_index")
+    return idx, scores, sim
+
+
 def _host_rows(fn: str, rows, n: int) -> np.ndarray:
     """Row numbers given on the host (a sequence or a CPU tensor), checked: int64 [R], integers (TypeError) inside [0, n) (IndexError)."""
     r = np.asarray(rows.numpy() if hasattr(rows, "numpy") else rows).reshape(-1)
@@ -182,7 +229,8 @@ def _host_rows(fn: str, rows, n: int) -> np.ndarray:
 
 
 class GalleryIndex:
-    """A gallery that stays on the device between searches: a few queries at a time against a corpus that changes row by row, if at all.
+    """A gallery that stays on the device between searches: a few queries at a time, or a whole query set, against a corpus that changes
+    row by row, if at all.
 
     GalleryIndex(gallery, normalize=True, storage=None, capacity=None): gallery is a cuda float32, bfloat16 or float16 [N, d] tensor.
     storage=None keeps the tensor's own dtype, by reference when contiguous (a copy otherwise).  storage=torch.bfloat16 or
@@ -200,10 +248,12 @@ class GalleryIndex:
     to float32 — a 16-bit value widens exactly, so only the storage differs, not the arithmetic or the order.  queries are float32;
     queries [d] is one query.  1 <= k <= min(N, 128).
     M <= RETRIEVAL_FEW_MAX goes through coot_retrieval_topk_few_masked (any storage; without a filter it launches the kernels of
-    coot_retrieval_topk_few / coot_retrieval_topk_few_h) with the stored norms: one sweep of the gallery, one row per thread.  M > RETRIEVAL_FEW_MAX on a float32 index goes through retrieval_topk_device
-    unchanged, which recomputes the gallery norms on every call; on a 16-bit index it goes through the few-query call in slices of
-    16 queries (a query's result does not depend on its batch-mates, and no float32 copy of the gallery is made): ceil(M / 16) sweeps
-    of the gallery, so large query batches are not what 16-bit storage is for.
+    coot_retrieval_topk_few / coot_retrieval_topk_few_h) with the stored norms: one sweep of the gallery, one row per thread.
+    M > RETRIEVAL_FEW_MAX on a float32 index is one coot_retrieval_topk_index call (retrieval_topk_index_device): the tile search with
+    the stored norms, so no pass over the gallery recomputes them.  On a 16-bit index the same call serves M >= INDEX_TILE_MIN_M_16BIT
+    (the 16-bit rows are widened as they are staged; no float32 copy of the gallery is made); fewer queries go through the few-query
+    call in slices of 16 (a query's result does not depend on its batch-mates): ceil(M / 16) sweeps of the gallery, which up to there
+    take less time than the tile walk (measured: see the constant).
 
     Filtering.  search(..., keep=mask): mask is a cuda torch.bool or torch.uint8 tensor [N], nonzero = the row may be returned; the
     result is the bytes of the search on an index of gallery[mask] with its indices mapped back (compute_retrieval_topk_masked of the
@@ -457,15 +507,15 @@ class GalleryIndex:
         m = queries.shape[0]
         if self.keep is not None:  # the index's own filter AND the search's
             keep = self.keep.view(torch.uint8) if keep is None else (self.keep & (keep != 0)).view(torch.uint8)
-        if m > RETRIEVAL_FEW_MAX and not self._code:
-            return retrieval_topk_device(queries, self.gallery, k, normalize=self.normalize, want_sim=want_sim, keep=keep)
+        if m > RETRIEVAL_FEW_MAX and (not self._code or m >= INDEX_TILE_MIN_M_16BIT):
+            return retrieval_topk_index_device(queries, self.gallery, self.norms if self.normalize else None, k, keep=keep, want_sim=want_sim)
         queries = queries.contiguous()
         lib = _lib.load()
         ws, idx, scores, sim = _topk_buffers(lib.coot_retrieval_topk_few_workspace_bytes(min(m, RETRIEVAL_FEW_MAX), n, d, k), m, n, k, want_sim,
                                              queries.device)
         norms = self.norms.data_ptr() if self.normalize else None
         st = torch.cuda.current_stream().cuda_stream
-        for i in range(0, m, RETRIEVAL_FEW_MAX):  # one slice unless M > RETRIEVAL_FEW_MAX (16-bit storage only); the calls of a stream run in order: one workspace
+        for i in range(0, m, RETRIEVAL_FEW_MAX):  # one slice unless RETRIEVAL_FEW_MAX < M < INDEX_TILE_MIN_M_16BIT (16-bit storage only); the calls of a stream run in order: one workspace
             mm = min(RETRIEVAL_FEW_MAX, m - i)
             _lib.check(lib.coot_retrieval_topk_few_masked(queries[i:].data_ptr(), self.gallery.data_ptr(), self._code, norms,
                                                           None if keep is None else keep.data_ptr(), mm, n, d, k, idx[i:].data_ptr(),

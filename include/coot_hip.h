@@ -424,6 +424,26 @@ int coot_retrieval_topk_few_masked(const float* queries, const void* gallery, in
                                    const uint8_t* keep, int M, int N, int d, int K, int32_t* idx_out, float* score_out, float* sim_out,
                                    void* workspace, size_t workspace_bytes, coot_stream_t stream);
 
+/* ---- the tile search on a prepared gallery: many queries, any storage, stored norms -------------------------------------------
+ * coot_retrieval_topk_index: M >= 1 queries (fp32) against the gallery as a prepared index holds it, gallery_dtype COOT_GALLERY_F32,
+ * _BF16 or _F16, with the norms it already has.  idx_out, score_out [M, K] and the optional sim_out [M, N] are byte for byte what
+ *   coot_retrieval_topk_masked(queries, W, keep, M, N, d, K, gallery_norms != NULL, ...)
+ * writes, W = the gallery widened to fp32, whenever gallery_norms holds what coot_retrieval_row_norms / coot_retrieval_row_norms_h
+ * compute for it (NULL: rows used as they are): unfilled slots under a mask (-1, -inf) included, for every split count
+ * (coot_set_option("rt_topk_splits", n), as above), and so for M <= COOT_RETRIEVAL_FEW_MAX also the bytes of
+ * coot_retrieval_topk_few_masked.  The walk over 64 x 64 tiles, the FMA chain, the selection and the merge are those of
+ * coot_retrieval_topk; a gallery element is widened as it is staged, no widened copy is made, and the gallery's norms are read, not
+ * recomputed: one launch computes the M query norms, and no pass over the gallery precedes the search.  keep: as in the filtered
+ * searches above (NULL: none; without sim_out a tile of 64 rows that keeps nothing is skipped).
+ * workspace (8-byte aligned): coot_retrieval_topk_index_workspace_bytes(M, N, d, K), exact = M floats and M x splits x K 64-bit
+ * words, each rounded up to 256 bytes; it depends on the split option: set that first.  A refused call (unknown dtype, null
+ * pointer other than gallery_norms, keep and sim_out, M, N or d < 1, K outside 1 .. min(N, 128), a workspace one byte short) returns
+ * before any launch and writes nothing.  No allocation, no synchronisation; no pointer is retained. */
+size_t coot_retrieval_topk_index_workspace_bytes(int M, int N, int d, int K);
+int coot_retrieval_topk_index(const float* queries, const void* gallery, int gallery_dtype, const float* gallery_norms, const uint8_t* keep,
+                              int M, int N, int d, int K, int32_t* idx_out, float* score_out, float* sim_out, void* workspace,
+                              size_t workspace_bytes, coot_stream_t stream);
+
 /* ---- a prepared gallery that changes: rows written in place, their norms with them ---------------------------------------
  * coot_retrieval_rows_put writes the R rows of src [R, d] into the buffer gallery [N, d] and, where norms != NULL, norms[row] of
  * every row it wrote: what a corpus that grows (rows appended into spare capacity) or is re-encoded (rows overwritten) needs,
