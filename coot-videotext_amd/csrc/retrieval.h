@@ -1,4 +1,4 @@
-// What the retrieval sources share (retrieval_tile.hip, retrieval_few.hip, retrieval_index.hip): the chunk constants and the widening of a
+// What the retrieval sources share (retrieval_tile.hip, retrieval_few.hip, retrieval_grouped.hip, retrieval_index.hip): the chunk constants and the widening of a
 // gallery element, the 64-bit top-K entry and the fold of candidates into a sorted list, and the host helpers that carve a workspace
 // and turn a run-time value into a template argument.  Every kernel is instantiated in one file only.
 #pragma once
@@ -11,11 +11,25 @@ namespace coot {
 // rt_norms_kernel<float> (retrieval_index.hip) on rows [0, Ma) of a, then [0, Nb) of b; the caller checks the launch
 void rt_launch_norms(const float* a, int Ma, const float* b, int Nb, int d, float* na, float* nb, hipStream_t st);
 
+// The few-query sweep's plan and the launches of its kernels that the grouped search shares (retrieval_few.hip):
+// few_plan: row splits and the 128-row blocks each one sweeps (every split has at least one block; cap bounds S whatever the option says);
+// rt_few_launch_prep: rt_few_prep_kernel, the query norms [16] and the operand table qn [d rounded up to 32][16];
+// rt_few_merge_lists: the merge by rank of S >= 2 sorted lists per query, lists [M][S][K], into idx_out / score_out, in rounds of <= 32
+//   lists; spare takes every other round's lists (M x ceil(S / 32) x K entries, unused for S <= 32).  Both return a launch's error.
+struct FewPlan { int MQ, S, blocks, cap; };
+FewPlan few_plan(int M, int N);
+int rt_few_launch_prep(const float* queries, int M, int d, bool norm, float* qnorm, float* qn, hipStream_t st);
+int rt_few_merge_lists(const unsigned long long* lists, unsigned long long* spare, int S, int M, int K, bool masked, int32_t* idx_out, float* score_out,
+                       hipStream_t st);
+
 namespace {
 
 constexpr int RT = 64;   // tile: 64 rows of emb1 x 64 rows of emb2
 constexpr int RK = 32;   // k chunk
 constexpr int RP = RK + 1;
+constexpr int FEW_MAX = COOT_RETRIEVAL_FEW_MAX;  // queries of a few-query sweep
+constexpr int FR = 128;                          // gallery rows per step of the sweep = threads per workgroup
+constexpr int FEW_G = 32;                        // lists per merge workgroup
 
 // A gallery element as fp32: itself, a bfloat16 (unsigned short: the upper half of the fp32 word) or an IEEE half (v_cvt_f32_f16).
 // Both 16-bit formats widen exactly, so whatever follows sees the operands of the widened fp32 copy.
@@ -35,6 +49,32 @@ __device__ __forceinline__ float row_sumsq(const T* src, int d, int lane) {
   float s = 0.f;
   for (int c = lane; c < d; c += 64) { const float x = widen(src[c]); s += x * x; }
   return wave_sum(s);
+}
+
+// one chunk of the chain for the thread's gallery row: acc[i] = fmaf(q_ik, g_jk, acc[i]) over the chunk's 32 k in order.  The 16-bit
+// sweep and the grouped sweep call it; the fp32 sweep of rt_few_kernel keeps the same loop in its body, so that its instantiations
+// compile to the instructions they had
+template <int MQ>
+__device__ __forceinline__ void few_fma_chunk(const float* tile, const float* qs, int tid, float (&acc)[MQ]) {
+#pragma unroll 4
+  for (int k = 0; k < RK; ++k) {
+    const float bv = tile[tid * RP + k];
+    float qv[MQ];
+    if constexpr (MQ >= 4) {
+#pragma unroll
+      for (int u = 0; u < MQ / 4; ++u) {
+        const float4 t = *(const float4*)(qs + k * FEW_MAX + 4 * u);
+        qv[4 * u] = t.x; qv[4 * u + 1] = t.y; qv[4 * u + 2] = t.z; qv[4 * u + 3] = t.w;
+      }
+    } else if constexpr (MQ == 2) {
+      const float2 t = *(const float2*)(qs + k * FEW_MAX);
+      qv[0] = t.x; qv[1] = t.y;
+    } else {
+      qv[0] = qs[k * FEW_MAX];
+    }
+#pragma unroll
+    for (int i = 0; i < MQ; ++i) acc[i] = fmaf(qv[i], bv, acc[i]);
+  }
 }
 
 // ---- the top-K entry ------------------------------------------------------------------------------------------------------------

@@ -24,10 +24,7 @@
 namespace coot {
 namespace {
 
-constexpr int FEW_MAX = COOT_RETRIEVAL_FEW_MAX;  // queries
-constexpr int FR = 128;                          // gallery rows per step = threads per workgroup
 constexpr int FEW_SMAX = 1024;                   // row splits: about four workgroups per CU
-constexpr int FEW_G = 32;                        // lists per merge workgroup
 constexpr int FEW_MT = 1024;                     // threads of a merge workgroup: the searches are LDS latency, so as many waves as fit
 int g_rt_few_splits = 0;                         // coot_set_option("rt_few_splits", n) (tests); 0 = automatic
 static_assert(FEW_MAX * FR * 8 <= (FR * RP + RK * FEW_MAX) * 4, "the candidate buffer lies over the staged tile");
@@ -46,31 +43,6 @@ __global__ __launch_bounds__(64) void rt_few_prep_kernel(const float* q, int M, 
 }
 
 size_t few_lds_bytes(int MQ, int K) { return (size_t)(FR * RP + RK * FEW_MAX) * 4 + (size_t)MQ * K * 8 + 2 * FEW_MAX * 4; }
-
-// one chunk of the chain for the thread's gallery row: acc[i] = fmaf(q_ik, g_jk, acc[i]) over the chunk's 32 k in order.  The 16-bit
-// sweep calls it; the fp32 sweep keeps the same loop in its body, so that its instantiations compile to the instructions they had
-template <int MQ>
-__device__ __forceinline__ void few_fma_chunk(const float* tile, const float* qs, int tid, float (&acc)[MQ]) {
-#pragma unroll 4
-  for (int k = 0; k < RK; ++k) {
-    const float bv = tile[tid * RP + k];
-    float qv[MQ];
-    if constexpr (MQ >= 4) {
-#pragma unroll
-      for (int u = 0; u < MQ / 4; ++u) {
-        const float4 t = *(const float4*)(qs + k * FEW_MAX + 4 * u);
-        qv[4 * u] = t.x; qv[4 * u + 1] = t.y; qv[4 * u + 2] = t.z; qv[4 * u + 3] = t.w;
-      }
-    } else if constexpr (MQ == 2) {
-      const float2 t = *(const float2*)(qs + k * FEW_MAX);
-      qv[0] = t.x; qv[1] = t.y;
-    } else {
-      qv[0] = qs[k * FEW_MAX];
-    }
-#pragma unroll
-    for (int i = 0; i < MQ; ++i) acc[i] = fmaf(qv[i], bv, acc[i]);
-  }
-}
 
 // grid (S); MQ = M rounded up to 1, 2, 4, 8, 16 accumulators; LDS: tile [FR][RP] | qs [RK][16] | list [MQ][K] | cnt | ncand
 // GT: the gallery's element type, float, unsigned short (bfloat16) or _Float16
@@ -293,9 +265,9 @@ __global__ __launch_bounds__(FEW_MT) void rt_few_merge_kernel(const tk_entry_t* 
   }
 }
 
+}  // namespace
 // row splits and the 128-row blocks each one sweeps: every split has at least one block.  cap bounds S whatever the option says:
 // the workspace is sized by it, so it does not depend on the option and stops growing with N.
-struct FewPlan { int MQ, S, blocks, cap; };
 FewPlan few_plan(int M, int N) {
   FewPlan p;
   p.MQ = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : M <= 8 ? 8 : 16;
@@ -306,6 +278,29 @@ FewPlan few_plan(int M, int N) {
   p.blocks = (nb + S - 1) / S; p.S = (nb + p.blocks - 1) / p.blocks;
   return p;
 }
+int rt_few_launch_prep(const float* queries, int M, int d, bool norm, float* qnorm, float* qn, hipStream_t st) {
+  hipLaunchKernelGGL(rt_few_prep_kernel, dim3(FEW_MAX), dim3(64), 0, st, queries, M, d, (d + RK - 1) / RK * RK, (int)norm, qnorm, qn);
+  COOT_CHECK_LAUNCH("rt_few_prep");
+  return 0;
+}
+// merge by rank in rounds of <= FEW_G lists, the two list buffers taking turns
+int rt_few_merge_lists(const tk_entry_t* lists, tk_entry_t* spare, int S, int M, int K, bool masked, int32_t* idx_out, float* score_out, hipStream_t st) {
+  const tk_entry_t* cur = lists;
+  tk_entry_t* nxt = spare;
+  while (S > FEW_G) {
+    const int So = (S + FEW_G - 1) / FEW_G;
+    hipLaunchKernelGGL((rt_few_merge_kernel<false, false>), dim3(So, M), dim3(FEW_MT), (size_t)FEW_G * K * 8, st, cur, S, K, nxt, So, (int*)nullptr, (float*)nullptr);
+    COOT_CHECK_LAUNCH("rt_few_merge");
+    tk_entry_t* done = nxt; nxt = (tk_entry_t*)cur; cur = done; S = So;
+  }
+  with_bool(masked, [&](auto mk) {
+    hipLaunchKernelGGL((rt_few_merge_kernel<true, decltype(mk)::value>), dim3(1, M), dim3(FEW_MT), (size_t)S * K * 8, st, cur, S, K,
+                       (tk_entry_t*)nullptr, 1, (int*)idx_out, score_out);
+  });
+  COOT_CHECK_LAUNCH("rt_few_merge");
+  return 0;
+}
+namespace {
 struct FewWs { float *qnorm, *qn; tk_entry_t *part_a, *part_b; size_t bytes; };
 FewWs few_layout(void* base, int M, int d, int K, int cap) {
   Arena a{(char*)base}; FewWs w;
@@ -329,8 +324,7 @@ int few_search(const char* fn, const float* queries, const GT* gallery, const fl
   const FewPlan p = few_plan(M, N);
   const FewWs w = few_layout(workspace, M, d, K, p.cap);
   COOT_REQUIRE(w.bytes <= workspace_bytes, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, w.bytes);
-  hipLaunchKernelGGL(rt_few_prep_kernel, dim3(FEW_MAX), dim3(64), 0, st, queries, M, d, (d + RK - 1) / RK * RK, gallery_norms != nullptr, w.qnorm, w.qn);
-  COOT_CHECK_LAUNCH("rt_few_prep");
+  if (int rc = rt_few_launch_prep(queries, M, d, gallery_norms != nullptr, w.qnorm, w.qn, st)) return rc;
   const int vec = d % (16 / (int)sizeof(GT)) == 0 && ((uintptr_t)gallery & 15) == 0;  // every row starts 16-byte aligned
   with_mq(p.MQ, [&](auto mq) {
     with_bool(gallery_norms != nullptr, keep != nullptr, [&](auto norm, auto masked) {
@@ -341,22 +335,7 @@ int few_search(const char* fn, const float* queries, const GT* gallery, const fl
   });
   COOT_CHECK_LAUNCH("rt_few");
   if (p.S == 1) return 0;
-  // merge by rank in rounds of <= FEW_G lists, the two list buffers taking turns
-  const tk_entry_t* cur = w.part_a;
-  tk_entry_t* nxt = w.part_b;
-  int S = p.S;
-  while (S > FEW_G) {
-    const int So = (S + FEW_G - 1) / FEW_G;
-    hipLaunchKernelGGL((rt_few_merge_kernel<false, false>), dim3(So, M), dim3(FEW_MT), (size_t)FEW_G * K * 8, st, cur, S, K, nxt, So, (int*)nullptr, (float*)nullptr);
-    COOT_CHECK_LAUNCH("rt_few_merge");
-    tk_entry_t* done = nxt; nxt = (tk_entry_t*)cur; cur = done; S = So;
-  }
-  with_bool(keep != nullptr, [&](auto masked) {
-    hipLaunchKernelGGL((rt_few_merge_kernel<true, decltype(masked)::value>), dim3(1, M), dim3(FEW_MT), (size_t)S * K * 8, st, cur, S, K,
-                       (tk_entry_t*)nullptr, 1, (int*)idx_out, score_out);
-  });
-  COOT_CHECK_LAUNCH("rt_few_merge");
-  return 0;
+  return rt_few_merge_lists(w.part_a, w.part_b, p.S, M, K, keep != nullptr, idx_out, score_out, st);
 }
 
 }  // namespace

@@ -17,6 +17,8 @@ restore): a keep flag per gallery row that the selection consults — the bytes 
 indices mapped back, without the copy.  Each search is one library call whatever the arguments: coot_retrieval_topk_masked (tile),
 coot_retrieval_topk_index (tile, on an index) and coot_retrieval_topk_few_masked (few queries, any storage), which with keep = NULL
 launch what coot_retrieval_topk, coot_retrieval_topk_few and coot_retrieval_topk_few_h launch.
+Grouped search (compute_retrieval_topk_grouped / retrieval_topk_grouped_device / GalleryIndex.search_grouped): the K best GROUPS of
+gallery rows (the videos of a clip gallery), each through its best row, exact and byte-defined: coot_retrieval_topk_grouped.
 A gallery that changes (GalleryIndex.add / update / compact): rows appended into spare capacity or overwritten in place together with
 their norms (coot_retrieval_rows_put: O(R d) bytes, no synchronisation), removed rows dropped physically — after any sequence of
 them the index holds, byte for byte, what a fresh index on the same rows holds.
@@ -82,6 +84,39 @@ def compute_retrieval_topk_masked(sim: np.ndarray, k: int, keep) -> Tuple[np.nda
         idx[:, :c] = cols[sub_idx]
         scores[:, :c] = sub_scores
     return idx, scores
+
+
+def compute_retrieval_topk_grouped(sim: np.ndarray, k: int, groups, num_groups: Optional[int] = None, keep=None):
+    """The k best GROUPS of columns of every row of sim [M, N], each through its best column: (group int32 [M, k], idx int32 [M, k],
+    scores [M, k]).  groups [N] integers: groups[j] is the group of column j; num_groups = G (None: max(groups) + 1).  Per row: the
+    ranking of compute_retrieval_topk(sim, N) (score descending, then column descending) without the columns keep masks out (keep [N]
+    booleans or bytes, None: none) and without those whose group id lies outside [0, G); the first column of every group stays, and
+    the first k of those are the result.  1 <= k <= N whatever groups and keep hold; with fewer than k groups left the tail of a row is
+    group -1, idx -1, score -inf.  groups = arange(N): idx and scores of compute_retrieval_topk_masked, group == idx."""
+    sim = np.asarray(sim)
+    groups = np.asarray(groups).astype(np.int64).reshape(-1)
+    m, n = sim.shape
+    assert sim.ndim == 2 and 1 <= k <= n and groups.shape == (n,), (sim.shape, k, groups.shape)
+    g_total = max(int(groups.max()) + 1, 0) if num_groups is None else int(num_groups)
+    ok = (groups >= 0) & (groups < g_total)
+    if keep is not None:
+        keep = np.asarray(keep)
+        assert keep.shape == (n,), (keep.shape, n)
+        ok &= keep != 0
+    group = np.full((m, k), -1, np.int32)
+    idx = np.full((m, k), -1, np.int32)
+    scores = np.full((m, k), -np.inf, sim.dtype)
+    order = np.argsort(sim, axis=1, kind="stable")[:, ::-1]
+    for i in range(m):
+        seen, r = set(), 0
+        for j in order[i]:
+            if r == k:
+                break
+            if ok[j] and groups[j] not in seen:
+                seen.add(groups[j])
+                group[i, r], idx[i, r], scores[i, r] = groups[j], j, sim[i, j]
+                r += 1
+    return group, idx, scores
 
 
 def _check_keep(fn: str, keep, n: int):
@@ -214,6 +249,68 @@ def retrieval_topk_index_device(queries, gallery, norms, k: int, keep=None, want
                                              sim.data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
                "coot_retrieval_topk_index")
     return idx, scores, sim
+
+
+def _check_groups(fn: str, groups, n: int):
+    """The groups argument of a grouped search, checked on the host before anything is launched: a torch.int32 or torch.int64 tensor
+    [N] (ValueError), on the device (RuntimeError naming the host mirror).  Returns it as contiguous int32 (int64 is converted)."""
+    import torch
+    if not isinstance(groups, torch.Tensor) or groups.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{fn}: groups has to be a torch.int32 or torch.int64 tensor, not {getattr(groups, 'dtype', type(groups).__name__)}")
+    if tuple(groups.shape) != (n,):
+        raise ValueError(f"{fn}: groups of shape {tuple(groups.shape)}, a gallery of {n} rows (one group id per row: [{n}])")
+    if not groups.is_cuda:
+        raise RuntimeError(f"{fn} needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk_grouped)")
+    return groups.to(torch.int32).contiguous()
+
+
+def retrieval_topk_grouped_device(queries, gallery, norms, groups, k: int, num_groups=None, keep=None, want_sim: bool = False):
+    """The grouped search on a gallery as a prepared index holds it (coot_retrieval_topk_grouped): queries cuda float32 [M, d], gallery
+    cuda float32, bfloat16 or float16 [N, d], norms cuda float32 [N] (GalleryIndex.norms) or None: rows used as they are; groups cuda
+    torch.int32 or torch.int64 [N] (int64 is converted once), groups[j] = the group of gallery row j.  Returns (group int32 [M, k], idx
+    int32 [M, k], scores float32 [M, k], sim [M, N] or None) on the device: the k best groups of every query, each with its best row
+    and that row's score — compute_retrieval_topk_grouped of the similarities the other searches select from, byte for byte, without
+    the M x N matrix.  Rows that keep masks out and rows with a group id outside [0, num_groups) are never returned; with fewer than k
+    groups left the tail is group -1, idx -1, score -inf.  1 <= k <= min(N, 128), whatever groups and keep hold.
+    num_groups=None costs one synchronisation with the device (int(groups.max()) + 1): pass num_groups where it is known.  Otherwise
+    nothing synchronises.  More than 16 queries run in slices of 16, one sweep of the gallery each, over one workspace."""
+    import torch
+    from . import lib as _lib
+    fn = "retrieval_topk_grouped_device"
+    assert gallery.dim() == 2, gallery.shape
+    groups = _check_groups(fn, groups, gallery.shape[0])
+    if keep is not None:
+        keep = _check_keep(fn, keep, gallery.shape[0])
+    if not (queries.is_cuda and gallery.is_cuda and (norms is None or norms.is_cuda)):
+        raise RuntimeError(f"{fn} needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk_grouped)")
+    codes = _gallery_codes()
+    if gallery.dtype not in codes:
+        raise ValueError(f"{fn}: a gallery of dtype {gallery.dtype}; it has to be {_STORAGE_NAMES}")
+    if queries.dim() == 1:
+        queries = queries[None]
+    assert queries.dtype == torch.float32 and queries.dim() == 2, (queries.dtype, queries.shape)
+    (m, d), n, k = queries.shape, gallery.shape[0], int(k)
+    if gallery.shape[1] != d:
+        raise ValueError(f"{fn}: queries of width {d}, gallery of width {gallery.shape[1]}")
+    if not 1 <= k <= min(n, 128):
+        raise ValueError(f"{fn}: k = {k} is outside 1 .. min(N = {n}, 128)")
+    assert norms is None or (norms.dtype == torch.float32 and tuple(norms.shape) == (n,)), (norms.dtype, norms.shape, n)
+    g_total = int(groups.max()) + 1 if num_groups is None else int(num_groups)  # (None: the one synchronisation)
+    if g_total < 1:
+        raise ValueError(f"{fn}: num_groups = {g_total}; there has to be at least one group")
+    queries, gallery, norms = queries.contiguous(), gallery.contiguous(), None if norms is None else norms.contiguous()
+    lib = _lib.load()
+    ws, idx, scores, sim = _topk_buffers(lib.coot_retrieval_topk_grouped_workspace_bytes(min(m, RETRIEVAL_FEW_MAX), n, d, k, g_total), m, n, k, want_sim,
+                                         queries.device)
+    group = torch.empty_like(idx)
+    st = torch.cuda.current_stream().cuda_stream
+    for i in range(0, m, RETRIEVAL_FEW_MAX):  # the calls of a stream run in order: one workspace, its table reset by every call
+        mm = min(RETRIEVAL_FEW_MAX, m - i)
+        _lib.check(lib.coot_retrieval_topk_grouped(queries[i:].data_ptr(), gallery.data_ptr(), codes[gallery.dtype], None if norms is None else norms.data_ptr(),
+                                                   None if keep is None else keep.data_ptr(), groups.data_ptr(), g_total, mm, n, d, k, group[i:].data_ptr(),
+                                                   idx[i:].data_ptr(), scores[i:].data_ptr(), sim[i:].data_ptr() if want_sim else None, ws.data_ptr(),
+                                                   ws.numel(), st), "coot_retrieval_topk_grouped")
+    return group, idx, scores, sim
 
 
 def _host_rows(fn: str, rows, n: int) -> np.ndarray:
@@ -522,6 +619,38 @@ class GalleryIndex:
                                                           scores[i:].data_ptr(), sim[i:].data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(), st),
                        "coot_retrieval_topk_few_masked")
         return idx, scores, sim
+
+
+    def search_grouped(self, queries, k: int, groups, num_groups=None, keep=None, want_sim: bool = False):
+        """The k best GROUPS of rows for every query, each through its best row: (group int32 [M, k], idx int32 [M, k], scores float32
+        [M, k], sim [M, N] or None) on the device.  groups: a cuda torch.int32 or torch.int64 tensor [index.n], groups[j] = the group
+        of gallery row j (the video of a clip, a speaker, a cluster of near-duplicates).  Exact: compute_retrieval_topk_grouped of the
+        similarities search() selects from, byte for byte — with groups = arange(n) idx and scores are those of search(queries, k,
+        keep=keep) and group == idx; rows with an id outside [0, num_groups) are never returned; with fewer than k groups left the tail
+        is group -1, idx -1, score -inf.  keep and the index's own filter (remove) combine as in search.  1 <= k <= min(N, 128).
+        num_groups=None costs one synchronisation with the device (int(groups.max()) + 1): pass num_groups where it is known.
+        The index does not store groups; the caller owns the row-to-group table: after add() append to it, after compact() remap it
+        with the old row numbers compact returns (groups[old_rows]).  Any M: slices of 16 queries, one sweep of the gallery each
+        (retrieval_topk_grouped_device)."""
+        import torch
+        fn = "GalleryIndex.search_grouped"
+        groups = _check_groups(fn, groups, self.gallery.shape[0])
+        if keep is not None:
+            keep = _check_keep(fn, keep, self.gallery.shape[0])
+        if not queries.is_cuda:
+            raise RuntimeError(f"{fn} needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk_grouped)")
+        if queries.dim() == 1:
+            queries = queries[None]
+        (n, d), k = self.gallery.shape, int(k)
+        assert queries.dtype == torch.float32 and queries.dim() == 2, (queries.dtype, queries.shape)
+        if queries.shape[1] != d:
+            raise ValueError(f"{fn}: queries of width {queries.shape[1]}, gallery of width {d}")
+        if not 1 <= k <= min(n, 128):
+            raise ValueError(f"{fn}: k = {k} is outside 1 .. min(N = {n}, 128)")
+        if self.keep is not None:  # the index's own filter AND the search's
+            keep = self.keep if keep is None else self.keep & (keep != 0)
+        return retrieval_topk_grouped_device(queries, self.gallery, self.norms if self.normalize else None, groups, k, num_groups=num_groups, keep=keep,
+                                             want_sim=want_sim)
 
 
 def _ahead(s, idx, t, a):

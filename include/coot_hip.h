@@ -444,6 +444,30 @@ int coot_retrieval_topk_index(const float* queries, const void* gallery, int gal
                               int M, int N, int d, int K, int32_t* idx_out, float* score_out, float* sim_out, void* workspace,
                               size_t workspace_bytes, coot_stream_t stream);
 
+/* ---- grouped search: the K best groups of gallery rows, one row for each ------------------------------------------------------
+ * groups: device int32 [N], groups[j] = the group of gallery row j (the video of a clip, a speaker, a cluster of near-duplicates);
+ * num_groups = G.  For every query: take the ranking of all rows that coot_retrieval_topk defines (score descending, then row
+ * descending), drop the rows that keep masks out and the rows whose group id lies outside [0, G), keep the first row of every group,
+ * and return the first K of those: group_out, idx_out, score_out [M, K] = the group, its best row and that row's score, the fp32
+ * similarity of the searches above (the same FMA chain; sim_out [M, N], optional, holds every similarity).  With fewer than K groups
+ * left, the tail is group -1, idx -1, score -inf, the filtered searches' unfilled slot.  Exact: with groups[j] = j idx_out and
+ * score_out are byte for byte coot_retrieval_topk_few_masked's and group_out equals idx_out; with one group slot 0 is that search at
+ * K = 1.  An out-of-range id is never used as an index.
+ *   1 <= M <= COOT_RETRIEVAL_FEW_MAX, 1 <= K <= min(N, 128) (K is not checked against G or the mask), 1 <= num_groups <= 2^26;
+ *   gallery_dtype COOT_GALLERY_F32, _BF16 or _F16; gallery_norms NULL: rows used as they are; keep NULL: no filter.
+ * The few-query sweep (one gallery row per thread) raises a table best [M][G] of 64-bit top-K entries with an unsigned 64-bit atomic
+ * maximum: an entry is (score image, row) under a strict total order, so a group's best row does not depend on arrival order, nor
+ * the result on the sweep's row splits (coot_set_option("rt_few_splits", n)), the table ranges of the selection
+ * (coot_set_option("rt_grouped_splits", n), 0 = automatic) or the schedule.  The table is reset inside every call: nothing survives in
+ * a workspace.  workspace (16-byte aligned): coot_retrieval_topk_grouped_workspace_bytes(M, N, d, K, num_groups) = the query norms, the
+ * normalised queries, M x G entries and M x ranges x K entries of lists, ranges <= 256; it depends on neither option.  A refused call
+ * (unknown dtype, null pointer other than gallery_norms, keep and sim_out, M, K or num_groups outside its range, workspace misaligned
+ * or too small) returns before any launch and writes nothing.  No allocation, no synchronisation; no pointer is retained. */
+size_t coot_retrieval_topk_grouped_workspace_bytes(int M, int N, int d, int K, int num_groups);
+int coot_retrieval_topk_grouped(const float* queries, const void* gallery, int gallery_dtype, const float* gallery_norms, const uint8_t* keep,
+                                const int32_t* groups, int num_groups, int M, int N, int d, int K, int32_t* group_out, int32_t* idx_out,
+                                float* score_out, float* sim_out, void* workspace, size_t workspace_bytes, coot_stream_t stream);
+
 /* ---- a prepared gallery that changes: rows written in place, their norms with them ---------------------------------------
  * coot_retrieval_rows_put writes the R rows of src [R, d] into the buffer gallery [N, d] and, where norms != NULL, norms[row] of
  * every row it wrote: what a corpus that grows (rows appended into spare capacity) or is re-encoded (rows overwritten) needs,
