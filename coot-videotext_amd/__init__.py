@@ -16,7 +16,8 @@ from .retrieval import compute_retrieval, compute_retrieval_cosine, compute_retr
 from .retrieval import RETRIEVAL_FEW_MAX, GalleryIndex, compute_retrieval_topk_masked  # noqa: F401
 from .retrieval import retrieval_topk_index_device  # noqa: F401
 from .retrieval import compute_retrieval_topk_grouped, retrieval_topk_grouped_device  # noqa: F401
-from .retrieval import compute_retrieval_labeled, compute_retrieval_labeled_device, retrieval_ranks_labeled_device  # noqa: F401
+from .retrieval import compute_retrieval_topk_multi, retrieval_topk_multi_device  # noqa: F401
+from .retrieval import compute_retrieval_labeled,compute_retrieval_labeled_device, retrieval_ranks_labeled_device  # noqa: F401
 from .retrieval import compute_retrieval_counts_part, retrieval_metrics_device, retrieval_ranks_part_device  # noqa: F401
 from .trainer_retrieval import GradClip, LossScaler, RetrievalTrainer, make_optimizer  # noqa: F401
 from .validation import loader_order_permutation, save_embeddings, shard_batch_indices  # noqa: F401

@@ -1,4 +1,4 @@
-// What the retrieval sources share (retrieval_tile.hip, retrieval_few.hip, retrieval_grouped.hip, retrieval_index.hip): the chunk constants and the widening of a
+// What the retrieval sources share (retrieval_tile.hip, retrieval_few.hip, retrieval_grouped.hip, retrieval_multi.hip, retrieval_index.hip): the chunk constants and the widening of a
 // gallery element, the 64-bit top-K entry and the fold of candidates into a sorted list, and the host helpers that carve a workspace
 // and turn a run-time value into a template argument.  Every kernel is instantiated in one file only.
 #pragma once
@@ -22,6 +22,18 @@ int rt_few_launch_prep(const float* queries, int M, int d, bool norm, float* qno
 int rt_few_merge_lists(const unsigned long long* lists, unsigned long long* spare, int S, int M, int K, bool masked, int32_t* idx_out, float* score_out,
                        hipStream_t st);
 
+// What the multi-vector search shares with the grouped one (retrieval_grouped.hip):
+// grp_plan: the ranges of a table of NG groups that a selection walks (coot_set_option("rt_grouped_splits", n); cap bounds T whatever
+//   the option says, and a workspace is sized by it);
+// rt_grouped_launch_slice: rt_few_prep_kernel, then rt_grouped_kernel, for one slice of M <= 16 queries: the sweep raises best [M][NG],
+//   which the caller has reset, and writes sim [M][N] where it is given.  gallery_dtype: a COOT_GALLERY_* code the caller has checked;
+//   qnorm [16] and qn [d rounded up to 32][16]: the workspace of rt_few_launch_prep.  Returns a launch's error.
+struct GrpPlan { int T, span, cap; };
+GrpPlan grp_plan(int NG);
+int rt_grouped_launch_slice(const float* queries, const void* gallery, int gallery_dtype, const float* gallery_norms, const unsigned char* keep,
+                            const int32_t* groups, int NG, int M, int N, int d, float* sim, float* qnorm, float* qn, unsigned long long* best,
+                            hipStream_t st);
+
 namespace {
 
 constexpr int RT = 64;   // tile: 64 rows of emb1 x 64 rows of emb2
@@ -30,6 +42,8 @@ constexpr int RP = RK + 1;
 constexpr int FEW_MAX = COOT_RETRIEVAL_FEW_MAX;  // queries of a few-query sweep
 constexpr int FR = 128;                          // gallery rows per step of the sweep = threads per workgroup
 constexpr int FEW_G = 32;                        // lists per merge workgroup
+constexpr int GRP_GMAX = 1 << 26;                // groups of a grouped search: M x G entries of 8 bytes are the table
+constexpr int GRP_U = 4;                         // table loads in flight per lane of a table selection
 
 // A gallery element as fp32: itself, a bfloat16 (unsigned short: the upper half of the fp32 word) or an IEEE half (v_cvt_f32_f16).
 // Both 16-bit formats widen exactly, so whatever follows sees the operands of the widened fp32 copy.

@@ -16,15 +16,15 @@
 //     the result, several write lists [M][T][K] that rt_few_merge_kernel merges by rank ((-1, -inf) for the entry 0).
 //   rt_grouped_label_kernel: group_out = idx < 0 ? -1 : groups[idx] (after a merge; a single range labels its own result).
 // The result depends on neither the sweep's splits (rt_few_splits) nor the table's ranges (rt_grouped_splits).
+// rt_grouped_launch_slice (prep + sweep into a table the caller has reset) and grp_plan are shared with the multi-vector search
+// (retrieval_multi.hip), which runs a slice per 16 sentences into one table and selects on sums of its columns.
 #include "retrieval.h"
 
 namespace coot {
 namespace {
 
-constexpr int GRP_GMAX = 1 << 26;  // groups: M x G entries of 8 bytes are the table
 constexpr int GRP_RANGE_MIN = 16;  // table entries per range at least: the cap of the ranges is min(ceil(G / 16), GRP_TMAX)
 constexpr int GRP_TMAX = 256;      // ranges (lists per query before the merge)
-constexpr int GRP_U = 4;           // table loads in flight per lane of the selection
 int g_rt_grouped_splits = 0;       // coot_set_option("rt_grouped_splits", n) (tests); 0 = automatic
 
 // grid (S), 128 threads; MQ, GT, NORM, MASKED as in rt_few_kernel; LDS: tile [FR][RP] | qs [RK][16]
@@ -188,8 +188,8 @@ __global__ __launch_bounds__(256) void rt_grouped_label_kernel(const int* __rest
   if (e < n) group_out[e] = idx[e] < 0 ? -1 : groups[idx[e]];
 }
 
+}  // namespace
 // the ranges of the table: cap bounds T whatever the option says, and the workspace is sized by it
-struct GrpPlan { int T, span, cap; };
 GrpPlan grp_plan(int NG) {
   GrpPlan p;
   const int most = (NG + GRP_RANGE_MIN - 1) / GRP_RANGE_MIN;
@@ -199,6 +199,27 @@ GrpPlan grp_plan(int NG) {
   p.span = (NG + T - 1) / T; p.T = (NG + p.span - 1) / p.span;
   return p;
 }
+// prep + sweep of one slice of M <= FEW_MAX queries into a table the caller has reset (the grouped search: its only slice; the
+// multi-vector search, retrieval_multi.hip: every 16 sentences)
+int rt_grouped_launch_slice(const float* queries, const void* gallery, int gallery_dtype, const float* gallery_norms, const unsigned char* keep,
+                            const int32_t* groups, int NG, int M, int N, int d, float* sim, float* qnorm, float* qn, tk_entry_t* best, hipStream_t st) {
+  if (int rc = rt_few_launch_prep(queries, M, d, gallery_norms != nullptr, qnorm, qn, st)) return rc;
+  const FewPlan p = few_plan(M, N);
+  with_elem(gallery_dtype, [&](auto t) {
+    using GT = typename decltype(t)::type;
+    const int vec = d % (16 / (int)sizeof(GT)) == 0 && ((uintptr_t)gallery & 15) == 0;  // every row starts 16-byte aligned
+    with_mq(p.MQ, [&](auto mq) {
+      with_bool(gallery_norms != nullptr, keep != nullptr, [&](auto norm, auto masked) {
+        hipLaunchKernelGGL((rt_grouped_kernel<GT, decltype(mq)::value, decltype(norm)::value, decltype(masked)::value>), dim3(p.S), dim3(FR),
+                           (size_t)(FR * RP + RK * FEW_MAX) * 4, st, (const GT*)gallery, gallery_norms, (const float*)qn, M, N, d, p.blocks, vec, sim, keep,
+                           (const int*)groups, NG, best);
+      });
+    });
+  });
+  COOT_CHECK_LAUNCH("rt_grouped");
+  return 0;
+}
+namespace {
 struct GrpWs { float *qnorm, *qn; tk_entry_t *best, *part_a, *part_b; size_t bytes; };
 GrpWs grp_layout(void* base, int M, int d, int K, int NG, int cap) {
   Arena a{(char*)base}; GrpWs w;
@@ -211,30 +232,19 @@ GrpWs grp_layout(void* base, int M, int d, int K, int NG, int cap) {
   return w;
 }
 
-template <typename GT>
-int grouped_search(const char* fn, const float* queries, const GT* gallery, const float* gallery_norms, const unsigned char* keep, const int32_t* groups,
-                   int NG, int M, int N, int d, int K, int32_t* group_out, int32_t* idx_out, float* score_out, float* sim_out, void* workspace,
-                   size_t workspace_bytes, hipStream_t st) {
+int grouped_search(const char* fn, const float* queries, const void* gallery, int gallery_dtype, const float* gallery_norms, const unsigned char* keep,
+                   const int32_t* groups, int NG, int M, int N, int d, int K, int32_t* group_out, int32_t* idx_out, float* score_out, float* sim_out,
+                   void* workspace, size_t workspace_bytes, hipStream_t st) {
   COOT_REQUIRE(queries && gallery && groups && group_out && idx_out && score_out && workspace, "%s: null pointer", fn);
   COOT_REQUIRE(M >= 1 && M <= FEW_MAX && N >= 1 && d >= 1, "%s: M = %d (1 .. %d), N = %d, d = %d", fn, M, FEW_MAX, N, d);
   COOT_REQUIRE(K >= 1 && K <= N && K <= TK_MAX, "%s: K = %d is outside 1 .. min(N = %d, %d)", fn, K, N, TK_MAX);
   COOT_REQUIRE(NG >= 1 && NG <= GRP_GMAX, "%s: num_groups = %d is outside 1 .. %d", fn, NG, GRP_GMAX);
   COOT_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: workspace is not 16-byte aligned", fn);
-  const FewPlan p = few_plan(M, N);
   const GrpPlan gp = grp_plan(NG);
   const GrpWs w = grp_layout(workspace, M, d, K, NG, gp.cap);
   COOT_REQUIRE(w.bytes <= workspace_bytes, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, w.bytes);
-  if (int rc = rt_few_launch_prep(queries, M, d, gallery_norms != nullptr, w.qnorm, w.qn, st)) return rc;
   if (int rc = check_hip(hipMemsetAsync(w.best, 0, (size_t)M * NG * sizeof(tk_entry_t), st), "rt_grouped table reset")) return rc;
-  const int vec = d % (16 / (int)sizeof(GT)) == 0 && ((uintptr_t)gallery & 15) == 0;  // every row starts 16-byte aligned
-  with_mq(p.MQ, [&](auto mq) {
-    with_bool(gallery_norms != nullptr, keep != nullptr, [&](auto norm, auto masked) {
-      hipLaunchKernelGGL((rt_grouped_kernel<GT, decltype(mq)::value, decltype(norm)::value, decltype(masked)::value>), dim3(p.S), dim3(FR),
-                         (size_t)(FR * RP + RK * FEW_MAX) * 4, st, gallery, gallery_norms, (const float*)w.qn, M, N, d, p.blocks, vec, sim_out, keep,
-                         (const int*)groups, NG, w.best);
-    });
-  });
-  COOT_CHECK_LAUNCH("rt_grouped");
+  if (int rc = rt_grouped_launch_slice(queries, gallery, gallery_dtype, gallery_norms, keep, groups, NG, M, N, d, sim_out, w.qnorm, w.qn, w.best, st)) return rc;
   hipLaunchKernelGGL(rt_grouped_select_kernel, dim3(gp.T, M), dim3(64), 0, st, (const tk_entry_t*)w.best, (const int*)groups, NG, K, gp.span, gp.T, w.part_a,
                      (int*)group_out, (int*)idx_out, score_out);
   COOT_CHECK_LAUNCH("rt_grouped_select");
@@ -265,10 +275,8 @@ int coot_retrieval_topk_grouped(const float* queries, const void* gallery, int g
   const char* fn = "retrieval_topk_grouped";
   COOT_REQUIRE(gallery_dtype == COOT_GALLERY_F32 || gallery_dtype == COOT_GALLERY_BF16 || gallery_dtype == COOT_GALLERY_F16,
                "%s: gallery_dtype = %d (COOT_GALLERY_F32, COOT_GALLERY_BF16 or COOT_GALLERY_F16)", fn, gallery_dtype);
-  return with_elem(gallery_dtype, [&](auto t) {
-    return grouped_search(fn, queries, (const typename decltype(t)::type*)gallery, gallery_norms, keep, groups, num_groups, M, N, d, K, group_out,
-                          idx_out, score_out, sim_out, workspace, workspace_bytes, (hipStream_t)stream);
-  });
+  return grouped_search(fn, queries, gallery, gallery_dtype, gallery_norms, keep, groups, num_groups, M, N, d, K, group_out, idx_out, score_out, sim_out,
+                        workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

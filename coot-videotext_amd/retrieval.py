@@ -19,6 +19,9 @@ coot_retrieval_topk_index (tile, on an index) and coot_retrieval_topk_few_masked
 launch what coot_retrieval_topk, coot_retrieval_topk_few and coot_retrieval_topk_few_h launch.
 Grouped search (compute_retrieval_topk_grouped / retrieval_topk_grouped_device / GalleryIndex.search_grouped): the K best GROUPS of
 gallery rows (the videos of a clip gallery), each through its best row, exact and byte-defined: coot_retrieval_topk_grouped.
+Multi-vector search (compute_retrieval_topk_multi / retrieval_topk_multi_device / GalleryIndex.search_multi): the K best groups for a
+PARAGRAPH of queries, a group's score the sum over the sentences of each sentence's best row in it (MaxSim), with the row that answers
+every sentence: coot_retrieval_topk_multi, the grouped search's table summed over column segments.
 A gallery that changes (GalleryIndex.add / update / compact): rows appended into spare capacity or overwritten in place together with
 their norms (coot_retrieval_rows_put: O(R d) bytes, no synchronisation), removed rows dropped physically — after any sequence of
 them the index holds, byte for byte, what a fresh index on the same rows holds.
@@ -119,16 +122,91 @@ def compute_retrieval_topk_grouped(sim: np.ndarray, k: int, groups, num_groups: 
     return group, idx, scores
 
 
-def _check_keep(fn: str, keep, n: int):
+def _host_offsets(fn: str, offsets, m: int, exc=ValueError) -> np.ndarray:
+    """The offsets of a multi-vector search as int64 [P + 1], checked on the host: a sequence, numpy array or CPU integer tensor of at
+    least 2 entries, the first 0, the last M, none smaller than the one before it."""
+    if hasattr(offsets, "is_cuda"):
+        if offsets.is_cuda:
+            raise exc(f"{fn}: offsets live on the host (a sequence, a numpy array or a CPU integer tensor), not on {offsets.device}")
+        offsets = offsets.numpy()
+    try:
+        off = np.asarray(offsets)
+    except Exception:
+        off = np.asarray(None)
+    if off.ndim != 1 or off.dtype.kind not in "iu" or off.size < 2:
+        raise exc(f"{fn}: offsets has to be a sequence, numpy array or CPU tensor of at least 2 integers (P + 1 of them, paragraph p = "
+                  f"queries[offsets[p]:offsets[p + 1]]), not {type(offsets).__name__} of dtype {off.dtype} and shape {off.shape}")
+    off = off.astype(np.int64)
+    if off[0] != 0 or off[-1] != m:
+        raise exc(f"{fn}: offsets runs from {off[0]} to {off[-1]}; it has to start at 0 and end at M = {m}")
+    if (np.diff(off) < 0).any():
+        raise exc(f"{fn}: offsets decreases at entry {int(np.argmax(np.diff(off) < 0)) + 1}; it has to be non-decreasing")
+    return off
+
+
+def compute_retrieval_topk_multi(sim: np.ndarray, offsets, k: int, groups, num_groups: Optional[int] = None, keep=None):
+    """The k best GROUPS of columns for every PARAGRAPH of rows of sim [M, N] (MaxSim, late interaction): paragraph p is the rows
+    offsets[p] .. offsets[p + 1] - 1 (offsets: P + 1 integers from 0 to M, non-decreasing; a paragraph may be empty).  Returns (group
+    int32 [P, k], scores [P, k], rows int32 [M, k], row_scores [M, k]).  groups, num_groups = G and keep as in
+    compute_retrieval_topk_grouped, and so is the entry of row i in group g: the first column of g in the ranking of row i (score
+    descending, then column descending) without the columns keep masks out and those with an id outside [0, G); its score is sim[i, j]
+    with -0 as +0.  Group g is a candidate for paragraph p if p is not empty and every row of p has an entry in g; its score is s = +0,
+    then s = s + score(i, g) for the rows of p in order — float32 adds in exactly that order; candidates are ordered by score
+    descending, then GROUP id descending (the grouped search orders by row; a paragraph has no single row).  group, scores: the first k
+    candidates, the tail -1 / -inf.  rows, row_scores, the alignment: for row i of paragraph p, slot r holds the entry of i in
+    group[p, r], -1 / -inf where group[p, r] is -1.  1 <= k <= N whatever groups and keep hold."""
+    sim = np.asarray(sim)
+    groups = np.asarray(groups).astype(np.int64).reshape(-1)
+    assert sim.ndim == 2, sim.shape
+    m, n = sim.shape
+    assert 1 <= k <= n and groups.shape == (n,), (sim.shape, k, groups.shape)
+    off = _host_offsets("compute_retrieval_topk_multi", offsets, m, exc=AssertionError)
+    g_total = max(int(groups.max()) + 1, 0) if num_groups is None else int(num_groups)
+    ok = (groups >= 0) & (groups < g_total)
+    if keep is not None:
+        keep = np.asarray(keep)
+        assert keep.shape == (n,), (keep.shape, n)
+        ok &= keep != 0
+    # the table: entry of (row i, group g), -1 = none
+    best = np.full((m, g_total), -1, np.int64)
+    score = np.zeros((m, g_total), sim.dtype)
+    order = np.argsort(sim, axis=1, kind="stable")[:, ::-1]
+    for i in range(m):
+        o = order[i][ok[order[i]]]
+        first_g, first_at = np.unique(groups[o], return_index=True)
+        best[i, first_g] = o[first_at]
+        score[i, first_g] = sim[i, o[first_at]] + sim.dtype.type(0)  # -0 -> +0
+    p_total = len(off) - 1
+    group = np.full((p_total, k), -1, np.int32)
+    scores = np.full((p_total, k), -np.inf, sim.dtype)
+    rows = np.full((m, k), -1, np.int32)
+    row_scores = np.full((m, k), -np.inf, sim.dtype)
+    for p in range(p_total):
+        i0, i1 = int(off[p]), int(off[p + 1])
+        if i1 == i0:
+            continue
+        cand = np.nonzero((best[i0:i1] >= 0).all(axis=0))[0]
+        s = np.zeros(g_total, sim.dtype)
+        for i in range(i0, i1):  # one add per sentence, in order: np.sum and np.add.reduce add pairwise
+            s = s + score[i]
+        top = cand[np.argsort(s[cand], kind="stable")[::-1][:k]]  # ascending and stable, reversed: score, then group id, descending
+        c = len(top)
+        group[p, :c], scores[p, :c] = top, s[top]
+        rows[i0:i1, :c], row_scores[i0:i1, :c] = best[i0:i1][:, top], score[i0:i1][:, top]
+    return group, scores, rows, row_scores
+
+
+def _check_keep(fn: str, keep, n: int, mirror: str = "compute_retrieval_topk_masked"):
     """The keep argument of a filtered search, checked on the host before anything is launched: a torch.bool or torch.uint8 tensor
-    [N] (ValueError), on the device (RuntimeError naming the host mirror).  Returns it as contiguous bytes (a view where it can be)."""
+    [N] (ValueError), on the device (RuntimeError naming the host mirror; mirror=None: the caller checks the device).  Returns it as
+    contiguous bytes (a view where it can be)."""
     import torch
     if not isinstance(keep, torch.Tensor) or keep.dtype not in (torch.bool, torch.uint8):
         raise ValueError(f"{fn}: keep has to be a torch.bool or torch.uint8 tensor, not {getattr(keep, 'dtype', type(keep).__name__)}")
     if tuple(keep.shape) != (n,):
         raise ValueError(f"{fn}: keep of shape {tuple(keep.shape)}, a gallery of {n} rows (one flag per row: [{n}])")
-    if not keep.is_cuda:
-        raise RuntimeError(f"{fn} needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk_masked)")
+    if mirror is not None and not keep.is_cuda:
+        raise RuntimeError(f"{fn} needs CUDA tensors (there is no CPU fallback; use {mirror})")
     keep = keep.contiguous()
     return keep.view(torch.uint8) if keep.dtype is torch.bool else keep
 
@@ -251,16 +329,17 @@ def retrieval_topk_index_device(queries, gallery, norms, k: int, keep=None, want
     return idx, scores, sim
 
 
-def _check_groups(fn: str, groups, n: int):
+def _check_groups(fn: str, groups, n: int, mirror: str = "compute_retrieval_topk_grouped"):
     """The groups argument of a grouped search, checked on the host before anything is launched: a torch.int32 or torch.int64 tensor
-    [N] (ValueError), on the device (RuntimeError naming the host mirror).  Returns it as contiguous int32 (int64 is converted)."""
+    [N] (ValueError), on the device (RuntimeError naming the host mirror; mirror=None: the caller checks the device).  Returns it as
+    contiguous int32 (int64 is converted)."""
     import torch
     if not isinstance(groups, torch.Tensor) or groups.dtype not in (torch.int32, torch.int64):
         raise ValueError(f"{fn}: groups has to be a torch.int32 or torch.int64 tensor, not {getattr(groups, 'dtype', type(groups).__name__)}")
     if tuple(groups.shape) != (n,):
         raise ValueError(f"{fn}: groups of shape {tuple(groups.shape)}, a gallery of {n} rows (one group id per row: [{n}])")
-    if not groups.is_cuda:
-        raise RuntimeError(f"{fn} needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk_grouped)")
+    if mirror is not None and not groups.is_cuda:
+        raise RuntimeError(f"{fn} needs CUDA tensors (there is no CPU fallback; use {mirror})")
     return groups.to(torch.int32).contiguous()
 
 
@@ -311,6 +390,99 @@ def retrieval_topk_grouped_device(queries, gallery, norms, groups, k: int, num_g
                                                    idx[i:].data_ptr(), scores[i:].data_ptr(), sim[i:].data_ptr() if want_sim else None, ws.data_ptr(),
                                                    ws.numel(), st), "coot_retrieval_topk_grouped")
     return group, idx, scores, sim
+
+
+# retrieval_topk_multi_device: the table best [M][G] of one library call holds at most this many entries (2^25 x 8 bytes = 256 MiB); a
+# larger search runs as several calls, split where a paragraph ends, over one workspace.  One paragraph is never split: its own table
+# may reach the library's bound.
+MULTI_TABLE_ENTRIES = 1 << 25
+MULTI_TABLE_ENTRIES_MAX = 1 << 28  # coot_retrieval_topk_multi: M x num_groups of one call
+MULTI_PARAGRAPHS_MAX = 65535       # coot_retrieval_topk_multi: P of one call
+
+
+def _multi_calls(off: np.ndarray, g_total: int):
+    """The paragraphs [p0, p1) of each library call: as many as fit the table budget and the paragraph bound, at least one."""
+    calls, p0, p_total = [], 0, len(off) - 1
+    while p0 < p_total:
+        p1 = p0 + 1
+        while p1 < p_total and p1 - p0 < MULTI_PARAGRAPHS_MAX and (off[p1 + 1] - off[p0]) * g_total <= MULTI_TABLE_ENTRIES:
+            p1 += 1
+        calls.append((p0, p1))
+        p0 = p1
+    return calls
+
+
+def retrieval_topk_multi_device(queries, offsets, gallery, norms, groups, k: int, num_groups=None, keep=None, want_sim: bool = False):
+    """The multi-vector search on a gallery as a prepared index holds it (coot_retrieval_topk_multi): queries cuda float32 [M, d], the
+    sentences of P paragraphs concatenated; offsets: P + 1 integers ON THE HOST (a sequence, a numpy array or a CPU integer tensor), 0 =
+    offsets[0] <= ... <= offsets[P] = M, paragraph p = queries[offsets[p]:offsets[p + 1]], possibly empty; gallery, norms, groups,
+    num_groups and keep as in retrieval_topk_grouped_device.  Returns (group int32 [P, k], scores float32 [P, k], rows int32 [M, k],
+    row_scores float32 [M, k], sim [M, N] or None) on the device: the k best groups of every paragraph, a group's score the sum over
+    the paragraph's sentences, in order, of the sentence's best row in the group, ties to the larger group id; and for every sentence
+    the row that answered it in each of its paragraph's groups, with that row's score — compute_retrieval_topk_multi of the
+    similarities the other searches select from, byte for byte, without the M x N matrix.  A group in which some sentence of the
+    paragraph has no row left (keep, ids outside [0, num_groups)) is not returned; the tail is -1 / -inf, all of an empty paragraph's
+    slots.  1 <= k <= min(N, 128), whatever groups and keep hold.
+    offsets is checked here (ValueError) and uploaded, one small copy.  num_groups=None costs one synchronisation with the device
+    (int(groups.max()) + 1): pass num_groups where it is known.  Every 16 sentences are one sweep of the gallery into a table of M x
+    num_groups entries of 8 bytes; above MULTI_TABLE_ENTRIES entries the search runs as several library calls, split where a paragraph
+    ends (paragraphs are independent: the same bytes), and one paragraph above 2^28 entries is refused."""
+    import torch
+    from . import lib as _lib
+    fn = "retrieval_topk_multi_device"
+    assert gallery.dim() == 2, gallery.shape
+    groups = _check_groups(fn, groups, gallery.shape[0], mirror=None)  # types and shapes of all three first, then where they live
+    if keep is not None:
+        keep = _check_keep(fn, keep, gallery.shape[0], mirror=None)
+    assert queries.dim() == 2, queries.shape
+    off = _host_offsets(fn, offsets, queries.shape[0])
+    if not (queries.is_cuda and gallery.is_cuda and groups.is_cuda and (keep is None or keep.is_cuda) and (norms is None or norms.is_cuda)):
+        raise RuntimeError(f"{fn} needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk_multi)")
+    codes = _gallery_codes()
+    if gallery.dtype not in codes:
+        raise ValueError(f"{fn}: a gallery of dtype {gallery.dtype}; it has to be {_STORAGE_NAMES}")
+    assert queries.dtype == torch.float32, queries.dtype
+    (m, d), n, k = queries.shape, gallery.shape[0], int(k)
+    if gallery.shape[1] != d:
+        raise ValueError(f"{fn}: queries of width {d}, gallery of width {gallery.shape[1]}")
+    if not 1 <= k <= min(n, 128):
+        raise ValueError(f"{fn}: k = {k} is outside 1 .. min(N = {n}, 128)")
+    assert norms is None or (norms.dtype == torch.float32 and tuple(norms.shape) == (n,)), (norms.dtype, norms.shape, n)
+    g_total = int(groups.max()) + 1 if num_groups is None else int(num_groups)  # (None: the one synchronisation)
+    if g_total < 1:
+        raise ValueError(f"{fn}: num_groups = {g_total}; there has to be at least one group")
+    longest = int(np.diff(off).max())
+    if longest * g_total > MULTI_TABLE_ENTRIES_MAX:
+        raise ValueError(f"{fn}: a paragraph of {longest} sentences against {g_total} groups is a table of {longest * g_total} entries; "
+                         f"one paragraph has at most 2^28")
+    queries, gallery, norms = queries.contiguous(), gallery.contiguous(), None if norms is None else norms.contiguous()
+    dev, p_total = queries.device, len(off) - 1
+    group = torch.empty(p_total, k, dtype=torch.int32, device=dev)
+    scores = torch.empty(p_total, k, dtype=torch.float32, device=dev)
+    rows = torch.empty(m, k, dtype=torch.int32, device=dev)
+    row_scores = torch.empty(m, k, dtype=torch.float32, device=dev)
+    sim = torch.empty(m, n, dtype=torch.float32, device=dev) if want_sim else None
+    lib = _lib.load()
+    calls = _multi_calls(off, g_total)
+    # every call's offsets from its own first sentence, one after the other in one upload
+    rebased = np.concatenate([off[p0:p1 + 1] - off[p0] for p0, p1 in calls]).astype(np.int32)
+    dev_off = torch.from_numpy(rebased).to(dev)
+    ws = torch.empty(max(lib.coot_retrieval_topk_multi_workspace_bytes(p1 - p0, int(off[p1] - off[p0]), n, d, k, g_total) for p0, p1 in calls),
+                     dtype=torch.uint8, device=dev)
+    st = torch.cuda.current_stream().cuda_stream
+    nxt = 0
+    for p0, p1 in calls:  # the calls of a stream run in order: one workspace, its table reset by every call
+        i0, mm = int(off[p0]), int(off[p1] - off[p0])
+        at, nxt = nxt, nxt + p1 - p0 + 1
+        if mm == 0:  # nothing but empty paragraphs (behind a paragraph that fills a call): no sentence, no table, every slot the tail
+            group[p0:p1] = -1
+            scores[p0:p1] = float("-inf")
+            continue
+        _lib.check(lib.coot_retrieval_topk_multi(queries[i0:].data_ptr(), gallery.data_ptr(), codes[gallery.dtype], None if norms is None else norms.data_ptr(),
+                                                 None if keep is None else keep.data_ptr(), groups.data_ptr(), g_total, dev_off[at:].data_ptr(), p1 - p0, mm,
+                                                 n, d, k, group[p0:].data_ptr(), scores[p0:].data_ptr(), rows[i0:].data_ptr(), row_scores[i0:].data_ptr(),
+                                                 sim[i0:].data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(), st), "coot_retrieval_topk_multi")
+    return group, scores, rows, row_scores, sim
 
 
 def _host_rows(fn: str, rows, n: int) -> np.ndarray:
@@ -651,6 +823,36 @@ class GalleryIndex:
             keep = self.keep if keep is None else self.keep & (keep != 0)
         return retrieval_topk_grouped_device(queries, self.gallery, self.norms if self.normalize else None, groups, k, num_groups=num_groups, keep=keep,
                                              want_sim=want_sim)
+
+    def search_multi(self, queries, offsets, k: int, groups, num_groups=None, keep=None, want_sim: bool = False):
+        """The k best GROUPS of rows for every PARAGRAPH of queries, and which row answers each sentence (MaxSim, late interaction):
+        (group int32 [P, k], scores float32 [P, k], rows int32 [M, k], row_scores float32 [M, k], sim [M, N] or None) on the device.
+        queries cuda float32 [M, d]: the sentences of all paragraphs, concatenated; offsets: P + 1 integers on the host (a sequence, a
+        numpy array or a CPU integer tensor) from 0 to M, non-decreasing, paragraph p = queries[offsets[p]:offsets[p + 1]], possibly
+        empty; groups as in search_grouped (the video of a clip).  A group's score for a paragraph is the sum, over its sentences in
+        order, of the sentence's best row in the group — the score search_grouped gives that group — in float32, ties to the larger
+        group id; a group in which a sentence has no row left is not a candidate; the tail is -1 / -inf, all of an empty paragraph's
+        slots.  rows[i, r], row_scores[i, r]: the best row of sentence i in group[p, r] of its paragraph, and its score.  Exact:
+        compute_retrieval_topk_multi of the similarities search() selects from, byte for byte.  keep and the index's own filter (remove)
+        combine as in search.  1 <= k <= min(N, 128).  num_groups=None costs one synchronisation; the caller owns the row-to-group
+        table, as in search_grouped.  Any M: 16 sentences are one sweep of the gallery (retrieval_topk_multi_device)."""
+        fn = "GalleryIndex.search_multi"
+        groups = _check_groups(fn, groups, self.gallery.shape[0], mirror=None)
+        if keep is not None:
+            keep = _check_keep(fn, keep, self.gallery.shape[0], mirror=None)
+        assert queries.dim() == 2, queries.shape
+        _host_offsets(fn, offsets, queries.shape[0])
+        if not (queries.is_cuda and groups.is_cuda and (keep is None or keep.is_cuda)):
+            raise RuntimeError(f"{fn} needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk_multi)")
+        (n, d), k = self.gallery.shape, int(k)
+        if queries.shape[1] != d:
+            raise ValueError(f"{fn}: queries of width {queries.shape[1]}, gallery of width {d}")
+        if not 1 <= k <= min(n, 128):
+            raise ValueError(f"{fn}: k = {k} is outside 1 .. min(N = {n}, 128)")
+        if self.keep is not None:  # the index's own filter AND the search's
+            keep = self.keep if keep is None else self.keep & (keep != 0)
+        return retrieval_topk_multi_device(queries, offsets, self.gallery, self.norms if self.normalize else None, groups, k, num_groups=num_groups,
+                                           keep=keep, want_sim=want_sim)
 
 
 def _ahead(s, idx, t, a):

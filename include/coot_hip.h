@@ -468,6 +468,36 @@ int coot_retrieval_topk_grouped(const float* queries, const void* gallery, int g
                                 const int32_t* groups, int num_groups, int M, int N, int d, int K, int32_t* group_out, int32_t* idx_out,
                                 float* score_out, float* sim_out, void* workspace, size_t workspace_bytes, coot_stream_t stream);
 
+/* ---- multi-vector search: a paragraph's sentences against grouped rows (MaxSim, late interaction) -----------------------------
+ * queries [M, d] are the sentences of P paragraphs, concatenated; offsets: DEVICE int32 [P + 1], paragraph p = the query rows
+ * [offsets[p], offsets[p + 1]), which may be empty; a caller passes 0 = offsets[0] <= ... <= offsets[P] = M.  groups, num_groups = G and
+ * keep as in the grouped search.  The definition, byte for byte:
+ *   entry: best[i][g] = the first row of group g in sentence i's ranking of the kept rows with an id inside [0, G) (score descending,
+ *     then row descending): what the grouped search returns for g.  Its score is the fp32 similarity of the other searches, -0 as +0.
+ *   candidates: group g for paragraph p, if p is not empty and every sentence of p has an entry for g.
+ *   score: s = +0; for i = offsets[p] .. offsets[p + 1] - 1 ascending: s = s + score(best[i][g]) — plain fp32 adds in that order.
+ *   order: s descending, then GROUP id descending (the grouped search breaks ties by row; a paragraph has no single row).
+ * group_out, score_out [P, K]: the K first candidates of every paragraph, the tail (-1, -inf) where fewer exist, every slot of an
+ * empty paragraph.  row_out, row_score_out [M, K], the alignment: for sentence i of paragraph p, slot r = the row and score of
+ * best[i][group_out[p][r]], (-1, -inf) where group_out[p][r] is -1.  sim_out [M, N], optional: every similarity, mask or not.
+ * Sums that are NaN or infinite: no fault and no index out of range, otherwise unspecified.
+ *   1 <= P <= 65535, M >= 1, M x num_groups <= 2^28, 1 <= K <= min(N, 128) (not checked against G or the mask), 1 <= num_groups <= 2^26.
+ * The table best [M][G] of the grouped search is reset once, raised by the grouped search's sweep per 16 sentences, read once by a
+ * selection that sums column segments, and once per result slot by the alignment.  The result depends on neither split option
+ * ("rt_few_splits", "rt_grouped_splits": the ranges of the selection) nor the schedule; nothing survives in a workspace.
+ * offsets is read on the device and never trusted: a paragraph is clamped to i0 = clamp(offsets[p], 0, M), i1 = clamp(offsets[p + 1],
+ * i0, M); with entries out of order the alignment of a sentence follows the paragraph a binary search finds, if that one holds it,
+ * and is (-1, -inf) otherwise.  workspace (16-byte aligned): coot_retrieval_topk_multi_workspace_bytes(P, M, N, d, K, num_groups) = the
+ * operand table of one slice, M x G entries and P x ranges x K entries of lists, ranges <= 256; it needs no device, depends on neither
+ * option and is 256 for arguments out of range.  A refused call (unknown dtype, null pointer other than gallery_norms, keep and
+ * sim_out, P, M, K, num_groups or the table outside its range, workspace misaligned or too small) returns before any launch and
+ * writes nothing.  No allocation, no synchronisation; no pointer is retained. */
+size_t coot_retrieval_topk_multi_workspace_bytes(int P, int M, int N, int d, int K, int num_groups);
+int coot_retrieval_topk_multi(const float* queries, const void* gallery, int gallery_dtype, const float* gallery_norms, const uint8_t* keep,
+                              const int32_t* groups, int num_groups, const int32_t* offsets, int P, int M, int N, int d, int K,
+                              int32_t* group_out, float* score_out, int32_t* row_out, float* row_score_out, float* sim_out, void* workspace,
+                              size_t workspace_bytes, coot_stream_t stream);
+
 /* ---- a prepared gallery that changes: rows written in place, their norms with them ---------------------------------------
  * coot_retrieval_rows_put writes the R rows of src [R, d] into the buffer gallery [N, d] and, where norms != NULL, norms[row] of
  * every row it wrote: what a corpus that grows (rows appended into spare capacity) or is re-encoded (rows overwritten) needs,
