@@ -1,199 +1,52 @@
-"""Retrieval metrics, nntrainer/retrieval.py:31-98 semantics: rank of the diagonal item in argsort(row)[::-1]; R@K as
-fractions; medr = floor(median)+1; meanr = mean+1.
+"""The retrieval results for embeddings that live on the MI355X, computed by libcoot_hip.so.  No CPU fallback: CUDA tensors in,
+device kernels or an error that names the host mirror.  The mirrors themselves (numpy, the byte-exact definitions of everything
+below) are retrieval_mirror.py; their names are re-exported here.
 
-compute_retrieval / compute_retrieval_cosine: host (numpy) mirror of the reference functions, for CPU tensors.
-compute_retrieval_device: the same results for embeddings that live on the MI355X, computed by libcoot_hip.so
-(coot_retrieval_ranks_part + coot_retrieval_metrics: normalisation, similarities, both rank vectors and the metric dictionaries
-in four launches, the N x N matrix is never materialised).  No CPU fallback: CUDA tensors in, device kernels or an error.
+compute_retrieval_device: the dictionaries of compute_retrieval (coot_retrieval_ranks_part + coot_retrieval_metrics: normalisation,
+similarities, both rank vectors and the metric dictionaries in four launches, the N x N matrix is never materialised).
 
-compute_retrieval_topk / retrieval_topk_device: WHICH gallery items a query retrieves (the reference returns top1 only), for M
-queries against N gallery rows, M and N independent: the host mirror on a similarity matrix, and the tile search on the device
-(similarities and selection fused, no M x N matrix).  GalleryIndex: the same search on a gallery that stays on the device, its row
-norms computed once: a few queries at a time (the few-query search: the same bytes, one sweep of the gallery) or a whole query set
-(retrieval_topk_index_device: the tile search on the gallery as the index holds it, with the norms it has); the gallery may be held
-in bfloat16 or float16 (the bytes of the search on the gallery widened to fp32).
-Filtered search (compute_retrieval_topk_masked; keep= of retrieval_topk_device and GalleryIndex.search; GalleryIndex.remove /
-restore): a keep flag per gallery row that the selection consults — the bytes of the unfiltered search on gallery[keep] with its
-indices mapped back, without the copy.  Each search is one library call whatever the arguments: coot_retrieval_topk_masked (tile),
-coot_retrieval_topk_index (tile, on an index) and coot_retrieval_topk_few_masked (few queries, any storage), which with keep = NULL
-launch what coot_retrieval_topk, coot_retrieval_topk_few and coot_retrieval_topk_few_h launch.
-Grouped search (compute_retrieval_topk_grouped / retrieval_topk_grouped_device / GalleryIndex.search_grouped): the K best GROUPS of
-gallery rows (the videos of a clip gallery), each through its best row, exact and byte-defined: coot_retrieval_topk_grouped.
-Multi-vector search (compute_retrieval_topk_multi / retrieval_topk_multi_device / GalleryIndex.search_multi): the K best groups for a
-PARAGRAPH of queries, a group's score the sum over the sentences of each sentence's best row in it (MaxSim), with the row that answers
-every sentence: coot_retrieval_topk_multi, the grouped search's table summed over column segments.
-A gallery that changes (GalleryIndex.add / update / compact): rows appended into spare capacity or overwritten in place together with
-their norms (coot_retrieval_rows_put: O(R d) bytes, no synchronisation), removed rows dropped physically — after any sequence of
-them the index holds, byte for byte, what a fresh index on the same rows holds.
+retrieval_topk_device: WHICH gallery items a query retrieves (compute_retrieval_topk), M queries against N gallery rows: the tile
+search (similarities and selection fused, no M x N matrix).  GalleryIndex: the same search on a gallery that stays on the device, in
+float32, bfloat16 or float16, its row norms computed once: a few queries at a time (one sweep of the gallery) or a whole query set
+(retrieval_topk_index_device: the tile search on the gallery as the index holds it).  keep= / GalleryIndex.remove: a flag per gallery
+row that the selection consults (compute_retrieval_topk_masked).  One library call per search: coot_retrieval_topk_masked (tile),
+coot_retrieval_topk_index (tile, on an index), coot_retrieval_topk_few_masked (few queries, any storage).
+retrieval_topk_grouped_device / GalleryIndex.search_grouped: the K best GROUPS of gallery rows, each through its best row
+(compute_retrieval_topk_grouped): coot_retrieval_topk_grouped.  retrieval_topk_multi_device / GalleryIndex.search_multi: the K best
+groups for a PARAGRAPH of queries (compute_retrieval_topk_multi): coot_retrieval_topk_multi.
+The searches on a prepared gallery share one host check (_check_search) and have one implementation per library call (_topk_few,
+_topk_tile, _topk_grouped, _topk_multi), which the public wrapper and the GalleryIndex method both call.
+GalleryIndex.add / update / compact: rows appended or overwritten in place together with their norms (coot_retrieval_rows_put),
+removed rows dropped — the index then holds, byte for byte, what a fresh index on the same rows holds.
 
 Sharded validation (data-parallel runs): retrieval_ranks_part_device counts one strip of rows, an integer all-reduce of the
-strips is the whole (compute_retrieval_device(dp=...)), retrieval_metrics_device turns rank vectors into the metrics;
-compute_retrieval_counts_part is the host mirror of a strip.
-
-Labelled ranking (compute_retrieval_labeled / retrieval_ranks_labeled_device / compute_retrieval_labeled_device): the ranks and
-metrics without the assumption "square, ground truth on the diagonal" — M queries, N gallery rows, labels[i] = the gallery row of
-query i; several queries per row, rows without a query and queries without a row (a label outside [0, N)) are allowed."""
+strips is the whole (compute_retrieval_device(dp=...)), retrieval_metrics_device turns rank vectors into the metrics.
+Labelled ranking (retrieval_ranks_labeled_device / compute_retrieval_labeled_device): compute_retrieval_labeled on the device."""
 from __future__ import annotations
-
-import ctypes as C
-from typing import Dict, Optional, Tuple
 
 import numpy as np
 
-VALKEYS = ["r1", "r5", "r10", "r50", "medr", "meanr", "sum"]  # nntrainer/retrieval.py:12
+from .retrieval_mirror import (VALKEYS, _ahead, _host_offsets, _labeled_metrics, compute_retrieval, compute_retrieval_cosine,  # noqa: F401
+                               compute_retrieval_counts_part, compute_retrieval_labeled, compute_retrieval_topk, compute_retrieval_topk_grouped,
+                               compute_retrieval_topk_masked, compute_retrieval_topk_multi, strip_bounds)
 
 
-def compute_retrieval_cosine(dot_product: np.ndarray) -> Tuple[Dict[str, float], np.ndarray, np.ndarray]:
-    n = len(dot_product)
-    order = np.argsort(dot_product, axis=1)[:, ::-1]
-    ranks = np.argmax(order == np.arange(n)[:, None], axis=1).astype(np.float64)
-    top1 = order[:, 0].astype(np.float64)
-    r1, r5, r10, r50 = [float((ranks < k).mean()) for k in (1, 5, 10, 50)]
-    medr = float(np.floor(np.median(ranks)) + 1)
-    meanr = float(ranks.mean() + 1)
-    return {"r1": r1, "r5": r5, "r10": r10, "r50": r50, "medr": medr, "meanr": meanr, "sum": r1 + r5 + r50}, top1, ranks
+def _ptr(t):
+    """The address of a tensor for the library, NULL for None."""
+    return None if t is None else t.data_ptr()
 
 
-def compute_retrieval(emb1: np.ndarray, emb2: np.ndarray):
-    d = np.dot(emb1, emb2.T)
-    res1, _, _ = compute_retrieval_cosine(d)
-    res2, _, _ = compute_retrieval_cosine(d.T)
-    return res1, res2, (res1["r1"] + res2["r1"]) / 2
+def _stream():
+    """The handle of the current stream: every launch goes there."""
+    import torch
+    return torch.cuda.current_stream().cuda_stream
 
 
-def compute_retrieval_topk(sim: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray]:
-    """The k best columns of every row of sim [M, N], best first, and their scores: (idx int32 [M, k], scores [M, k]).  Order:
-    score descending, then column descending — a stable ascending argsort reversed, the tie rule of the device ranks (a later
-    index is ahead).  Column 0 is compute_retrieval_cosine's top1 wherever the row maximum is unique."""
-    sim = np.asarray(sim)
-    assert sim.ndim == 2 and 1 <= k <= sim.shape[1], (sim.shape, k)
-    idx = np.argsort(sim, axis=1, kind="stable")[:, ::-1][:, :k]
-    return idx.astype(np.int32), np.take_along_axis(sim, idx, axis=1)
-
-
-def compute_retrieval_topk_masked(sim: np.ndarray, k: int, keep) -> Tuple[np.ndarray, np.ndarray]:
-    """compute_retrieval_topk restricted to the columns with keep[j] != 0 (keep: [N] booleans or bytes): compute_retrieval_topk of
-    sim[:, keep] with its columns mapped back through np.nonzero(keep).  1 <= k <= N whatever the mask holds; with c < k kept
-    columns the slots r >= c of every row are idx = -1, score = -inf."""
-    sim = np.asarray(sim)
-    keep = np.asarray(keep)
-    assert sim.ndim == 2 and 1 <= k <= sim.shape[1] and keep.shape == (sim.shape[1],), (sim.shape, k, keep.shape)
-    cols = np.nonzero(keep)[0]
-    c = min(int(k), len(cols))
-    idx = np.full((sim.shape[0], k), -1, np.int32)
-    scores = np.full((sim.shape[0], k), -np.inf, sim.dtype)
-    if c:
-        sub_idx, sub_scores = compute_retrieval_topk(sim[:, cols], c)
-        idx[:, :c] = cols[sub_idx]
-        scores[:, :c] = sub_scores
-    return idx, scores
-
-
-def compute_retrieval_topk_grouped(sim: np.ndarray, k: int, groups, num_groups: Optional[int] = None, keep=None):
-    """The k best GROUPS of columns of every row of sim [M, N], each through its best column: (group int32 [M, k], idx int32 [M, k],
-    scores [M, k]).  groups [N] integers: groups[j] is the group of column j; num_groups = G (None: max(groups) + 1).  Per row: the
-    ranking of compute_retrieval_topk(sim, N) (score descending, then column descending) without the columns keep masks out (keep [N]
-    booleans or bytes, None: none) and without those whose group id lies outside [0, G); the first column of every group stays, and
-    the first k of those are the result.  1 <= k <= N whatever groups and keep hold; with fewer than k groups left the tail of a row is
-    group -1, idx -1, score -inf.  groups = arange(N): idx and scores of compute_retrieval_topk_masked, group == idx."""
-    sim = np.asarray(sim)
-    groups = np.asarray(groups).astype(np.int64).reshape(-1)
-    m, n = sim.shape
-    assert sim.ndim == 2 and 1 <= k <= n and groups.shape == (n,), (sim.shape, k, groups.shape)
-    g_total = max(int(groups.max()) + 1, 0) if num_groups is None else int(num_groups)
-    ok = (groups >= 0) & (groups < g_total)
-    if keep is not None:
-        keep = np.asarray(keep)
-        assert keep.shape == (n,), (keep.shape, n)
-        ok &= keep != 0
-    group = np.full((m, k), -1, np.int32)
-    idx = np.full((m, k), -1, np.int32)
-    scores = np.full((m, k), -np.inf, sim.dtype)
-    order = np.argsort(sim, axis=1, kind="stable")[:, ::-1]
-    for i in range(m):
-        seen, r = set(), 0
-        for j in order[i]:
-            if r == k:
-                break
-            if ok[j] and groups[j] not in seen:
-                seen.add(groups[j])
-                group[i, r], idx[i, r], scores[i, r] = groups[j], j, sim[i, j]
-                r += 1
-    return group, idx, scores
-
-
-def _host_offsets(fn: str, offsets, m: int, exc=ValueError) -> np.ndarray:
-    """The offsets of a multi-vector search as int64 [P + 1], checked on the host: a sequence, numpy array or CPU integer tensor of at
-    least 2 entries, the first 0, the last M, none smaller than the one before it."""
-    if hasattr(offsets, "is_cuda"):
-        if offsets.is_cuda:
-            raise exc(f"{fn}: offsets live on the host (a sequence, a numpy array or a CPU integer tensor), not on {offsets.device}")
-        offsets = offsets.numpy()
-    try:
-        off = np.asarray(offsets)
-    except Exception:
-        off = np.asarray(None)
-    if off.ndim != 1 or off.dtype.kind not in "iu" or off.size < 2:
-        raise exc(f"{fn}: offsets has to be a sequence, numpy array or CPU tensor of at least 2 integers (P + 1 of them, paragraph p = "
-                  f"queries[offsets[p]:offsets[p + 1]]), not {type(offsets).__name__} of dtype {off.dtype} and shape {off.shape}")
-    off = off.astype(np.int64)
-    if off[0] != 0 or off[-1] != m:
-        raise exc(f"{fn}: offsets runs from {off[0]} to {off[-1]}; it has to start at 0 and end at M = {m}")
-    if (np.diff(off) < 0).any():
-        raise exc(f"{fn}: offsets decreases at entry {int(np.argmax(np.diff(off) < 0)) + 1}; it has to be non-decreasing")
-    return off
-
-
-def compute_retrieval_topk_multi(sim: np.ndarray, offsets, k: int, groups, num_groups: Optional[int] = None, keep=None):
-    """The k best GROUPS of columns for every PARAGRAPH of rows of sim [M, N] (MaxSim, late interaction): paragraph p is the rows
-    offsets[p] .. offsets[p + 1] - 1 (offsets: P + 1 integers from 0 to M, non-decreasing; a paragraph may be empty).  Returns (group
-    int32 [P, k], scores [P, k], rows int32 [M, k], row_scores [M, k]).  groups, num_groups = G and keep as in
-    compute_retrieval_topk_grouped, and so is the entry of row i in group g: the first column of g in the ranking of row i (score
-    descending, then column descending) without the columns keep masks out and those with an id outside [0, G); its score is sim[i, j]
-    with -0 as +0.  Group g is a candidate for paragraph p if p is not empty and every row of p has an entry in g; its score is s = +0,
-    then s = s + score(i, g) for the rows of p in order — float32 adds in exactly that order; candidates are ordered by score
-    descending, then GROUP id descending (the grouped search orders by row; a paragraph has no single row).  group, scores: the first k
-    candidates, the tail -1 / -inf.  rows, row_scores, the alignment: for row i of paragraph p, slot r holds the entry of i in
-    group[p, r], -1 / -inf where group[p, r] is -1.  1 <= k <= N whatever groups and keep hold."""
-    sim = np.asarray(sim)
-    groups = np.asarray(groups).astype(np.int64).reshape(-1)
-    assert sim.ndim == 2, sim.shape
-    m, n = sim.shape
-    assert 1 <= k <= n and groups.shape == (n,), (sim.shape, k, groups.shape)
-    off = _host_offsets("compute_retrieval_topk_multi", offsets, m, exc=AssertionError)
-    g_total = max(int(groups.max()) + 1, 0) if num_groups is None else int(num_groups)
-    ok = (groups >= 0) & (groups < g_total)
-    if keep is not None:
-        keep = np.asarray(keep)
-        assert keep.shape == (n,), (keep.shape, n)
-        ok &= keep != 0
-    # the table: entry of (row i, group g), -1 = none
-    best = np.full((m, g_total), -1, np.int64)
-    score = np.zeros((m, g_total), sim.dtype)
-    order = np.argsort(sim, axis=1, kind="stable")[:, ::-1]
-    for i in range(m):
-        o = order[i][ok[order[i]]]
-        first_g, first_at = np.unique(groups[o], return_index=True)
-        best[i, first_g] = o[first_at]
-        score[i, first_g] = sim[i, o[first_at]] + sim.dtype.type(0)  # -0 -> +0
-    p_total = len(off) - 1
-    group = np.full((p_total, k), -1, np.int32)
-    scores = np.full((p_total, k), -np.inf, sim.dtype)
-    rows = np.full((m, k), -1, np.int32)
-    row_scores = np.full((m, k), -np.inf, sim.dtype)
-    for p in range(p_total):
-        i0, i1 = int(off[p]), int(off[p + 1])
-        if i1 == i0:
-            continue
-        cand = np.nonzero((best[i0:i1] >= 0).all(axis=0))[0]
-        s = np.zeros(g_total, sim.dtype)
-        for i in range(i0, i1):  # one add per sentence, in order: np.sum and np.add.reduce add pairwise
-            s = s + score[i]
-        top = cand[np.argsort(s[cand], kind="stable")[::-1][:k]]  # ascending and stable, reversed: score, then group id, descending
-        c = len(top)
-        group[p, :c], scores[p, :c] = top, s[top]
-        rows[i0:i1, :c], row_scores[i0:i1, :c] = best[i0:i1][:, top], score[i0:i1][:, top]
-    return group, scores, rows, row_scores
+def _on_device(fn: str, mirror: str, *tensors):
+    """CUDA tensors (None: not given), or the error that names the host mirror."""
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"{fn} needs CUDA tensors (there is no CPU fallback; use {mirror})")
 
 
 def _check_keep(fn: str, keep, n: int, mirror: str = "compute_retrieval_topk_masked"):
@@ -205,8 +58,8 @@ def _check_keep(fn: str, keep, n: int, mirror: str = "compute_retrieval_topk_mas
         raise ValueError(f"{fn}: keep has to be a torch.bool or torch.uint8 tensor, not {getattr(keep, 'dtype', type(keep).__name__)}")
     if tuple(keep.shape) != (n,):
         raise ValueError(f"{fn}: keep of shape {tuple(keep.shape)}, a gallery of {n} rows (one flag per row: [{n}])")
-    if mirror is not None and not keep.is_cuda:
-        raise RuntimeError(f"{fn} needs CUDA tensors (there is no CPU fallback; use {mirror})")
+    if mirror is not None:
+        _on_device(fn, mirror, keep)
     keep = keep.contiguous()
     return keep.view(torch.uint8) if keep.dtype is torch.bool else keep
 
@@ -214,8 +67,7 @@ def _check_keep(fn: str, keep, n: int, mirror: str = "compute_retrieval_topk_mas
 def _device_pair(fn: str, host: str, a, b, dtype, same_shape: bool = True, dim: int = 2):
     """The entry of every *_device wrapper: CUDA tensors or an error naming the host mirror, the dtype and the dimension
     asserted (and equal shapes, unless only the row width has to agree), contiguous copies returned."""
-    if not (a.is_cuda and b.is_cuda):
-        raise RuntimeError(f"{fn} needs CUDA tensors (there is no CPU fallback; use {host})")
+    _on_device(fn, host, a, b)
     assert a.dtype == dtype and b.dtype == dtype and a.dim() == dim and b.dim() == dim, (a.dtype, b.dtype, a.shape, b.shape)
     assert a.shape == b.shape if same_shape else a.shape[1] == b.shape[1], (a.shape, b.shape)
     return a.contiguous(), b.contiguous()
@@ -235,8 +87,7 @@ def retrieval_ranks_device(emb1, emb2, normalize: bool = False, want_sim: bool =
     met = torch.empty(2, 7, dtype=torch.float32, device=emb1.device)
     sim = torch.empty(n, n, dtype=torch.float32, device=emb1.device) if want_sim else None
     _lib.check(lib.coot_retrieval_ranks(emb1.data_ptr(), emb2.data_ptr(), n, d, int(normalize), r12.data_ptr(), r21.data_ptr(),
-                                        met.data_ptr(), sim.data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(),
-                                        torch.cuda.current_stream().cuda_stream), "coot_retrieval_ranks")
+                                        met.data_ptr(), _ptr(sim), ws.data_ptr(), ws.numel(), _stream()), "coot_retrieval_ranks")
     return r12, r21, met, sim
 
 
@@ -266,9 +117,8 @@ def retrieval_topk_device(queries, gallery, k: int, normalize: bool = False, wan
     (m, d), n, k = queries.shape, gallery.shape[0], int(k)
     lib = _lib.load()
     ws, idx, scores, sim = _topk_buffers(lib.coot_retrieval_topk_workspace_bytes(m, n, d, k), m, n, k, want_sim, queries.device)
-    _lib.check(lib.coot_retrieval_topk_masked(queries.data_ptr(), gallery.data_ptr(), None if keep is None else keep.data_ptr(), m, n, d, k,
-                                              int(normalize), idx.data_ptr(), scores.data_ptr(), sim.data_ptr() if want_sim else None, ws.data_ptr(),
-                                              ws.numel(), torch.cuda.current_stream().cuda_stream), "coot_retrieval_topk_masked")
+    _lib.check(lib.coot_retrieval_topk_masked(queries.data_ptr(), gallery.data_ptr(), _ptr(keep), m, n, d, k, int(normalize), idx.data_ptr(),
+                                              scores.data_ptr(), _ptr(sim), ws.data_ptr(), ws.numel(), _stream()), "coot_retrieval_topk_masked")
     return idx, scores, sim
 
 
@@ -301,32 +151,7 @@ def retrieval_topk_index_device(queries, gallery, norms, k: int, keep=None, want
     None) on the device, no synchronisation: the bytes of retrieval_topk_device(queries, gallery.float(), k, normalize=norms is not
     None, keep=keep), without the widened copy and without a pass over the gallery for its norms — they are read, not checked.
     Any M >= 1, 1 <= k <= min(N, 128); keep as in retrieval_topk_device."""
-    import torch
-    from . import lib as _lib
-    fn = "retrieval_topk_index_device"
-    if keep is not None:
-        assert gallery.dim() == 2, gallery.shape
-        keep = _check_keep(fn, keep, gallery.shape[0])
-    if not (queries.is_cuda and gallery.is_cuda and (norms is None or norms.is_cuda)):
-        raise RuntimeError(f"{fn} needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk" + ("_masked)" if keep is not None else ")"))
-    codes = _gallery_codes()
-    if gallery.dtype not in codes:
-        raise ValueError(f"{fn}: a gallery of dtype {gallery.dtype}; it has to be {_STORAGE_NAMES}")
-    assert queries.dtype == torch.float32 and queries.dim() == 2 and gallery.dim() == 2, (queries.dtype, queries.shape, gallery.shape)
-    (m, d), n, k = queries.shape, gallery.shape[0], int(k)
-    if gallery.shape[1] != d:
-        raise ValueError(f"{fn}: queries of width {d}, gallery of width {gallery.shape[1]}")
-    if not 1 <= k <= min(n, 128):
-        raise ValueError(f"{fn}: k = {k} is outside 1 .. min(N = {n}, 128)")
-    assert norms is None or (norms.dtype == torch.float32 and tuple(norms.shape) == (n,)), (norms.dtype, norms.shape, n)
-    queries, gallery, norms = queries.contiguous(), gallery.contiguous(), None if norms is None else norms.contiguous()
-    lib = _lib.load()
-    ws, idx, scores, sim = _topk_buffers(lib.coot_retrieval_topk_index_workspace_bytes(m, n, d, k), m, n, k, want_sim, queries.device)
-    _lib.check(lib.coot_retrieval_topk_index(queries.data_ptr(), gallery.data_ptr(), codes[gallery.dtype], None if norms is None else norms.data_ptr(),
-                                             None if keep is None else keep.data_ptr(), m, n, d, k, idx.data_ptr(), scores.data_ptr(),
-                                             sim.data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
-               "coot_retrieval_topk_index")
-    return idx, scores, sim
+    return _topk_tile(queries, gallery, norms, k, keep, want_sim)
 
 
 def _check_groups(fn: str, groups, n: int, mirror: str = "compute_retrieval_topk_grouped"):
@@ -338,9 +163,118 @@ def _check_groups(fn: str, groups, n: int, mirror: str = "compute_retrieval_topk
         raise ValueError(f"{fn}: groups has to be a torch.int32 or torch.int64 tensor, not {getattr(groups, 'dtype', type(groups).__name__)}")
     if tuple(groups.shape) != (n,):
         raise ValueError(f"{fn}: groups of shape {tuple(groups.shape)}, a gallery of {n} rows (one group id per row: [{n}])")
-    if mirror is not None and not groups.is_cuda:
-        raise RuntimeError(f"{fn} needs CUDA tensors (there is no CPU fallback; use {mirror})")
+    if mirror is not None:
+        _on_device(fn, mirror, groups)
     return groups.to(torch.int32).contiguous()
+
+
+def _gallery_code(fn: str, gallery):
+    """The COOT_GALLERY_* code of the gallery's dtype, or the ValueError."""
+    code = _gallery_codes().get(gallery.dtype)
+    if code is None:
+        raise ValueError(f"{fn}: a gallery of dtype {gallery.dtype}; it has to be {_STORAGE_NAMES}")
+    return code
+
+
+def _check_search(fn: str, mirror: str, queries, gallery, norms, k: int, detail=None, also=(), method=None, held: bool = False):
+    """The host checks every search on a prepared gallery ends with.  For a wrapper (fn), in this order: queries, gallery, norms and
+    `also` on the device (RuntimeError naming the mirror); the gallery's dtype (ValueError); float32 queries [M, d] (asserted, showing
+    `detail`); equal widths, 1 <= k <= min(N, 128) (ValueError); float32 norms [N] or None (asserted).  For a GalleryIndex method
+    (method: its name): what the caller brings first, under the method's name, then the index's gallery and norms under the wrapper's;
+    held: those are taken as the constructor left them (the few-query route of GalleryIndex.search, which has to stay short).
+    Returns the contiguous (queries, gallery, norms), the gallery's COOT_GALLERY_* code (held: None) and (m, n, d, k)."""
+    import torch
+    who = method or fn
+    _on_device(who, mirror, queries, *(() if method else (gallery, norms)), *also)
+    code = None if method else _gallery_code(fn, gallery)
+    assert queries.dtype == torch.float32 and queries.dim() == 2 and gallery.dim() == 2, detail or (queries.dtype, queries.shape)
+    (m, d), n, k = queries.shape, gallery.shape[0], int(k)
+    if gallery.shape[1] != d:
+        raise ValueError(f"{who}: queries of width {d}, gallery of width {gallery.shape[1]}")
+    if not 1 <= k <= min(n, 128):
+        raise ValueError(f"{who}: k = {k} is outside 1 .. min(N = {n}, 128)")
+    if held:
+        return (queries.contiguous(), gallery, norms), None, (m, n, d, k)
+    if method is not None:
+        _on_device(fn, mirror, gallery, norms)
+        code = _gallery_code(fn, gallery)
+    assert norms is None or (norms.dtype == torch.float32 and tuple(norms.shape) == (n,)), (norms.dtype, norms.shape, n)
+    return (queries.contiguous(), gallery.contiguous(), None if norms is None else norms.contiguous()), code, (m, n, d, k)
+
+
+def _and_own(own, keep):
+    """The checked keep of one search (bytes or None) ANDed with the filter an index holds itself (None: none), as bytes."""
+    if own is None:
+        return keep
+    import torch
+    return (own if keep is None else own & (keep != 0)).view(torch.uint8)
+
+
+def _topk_few(index, queries, k: int, keep, want_sim: bool):
+    """coot_retrieval_topk_few_masked on an index (GalleryIndex.search): slices of RETRIEVAL_FEW_MAX queries over one workspace; [d] is one query."""
+    from . import lib as _lib
+    fn, gallery, norms, code = "GalleryIndex.search", index.gallery, index.norms if index.normalize else None, index._code
+    if keep is not None:
+        keep = _check_keep(fn, keep, gallery.shape[0])
+    queries = queries[None] if queries.dim() == 1 else queries
+    (queries, gallery, norms), _, (m, n, d, k) = _check_search(fn, "compute_retrieval_topk", queries, gallery, norms, k, method=fn, held=True)
+    keep = _and_own(index.keep, keep)
+    lib = _lib.load()
+    ws, idx, scores, sim = _topk_buffers(lib.coot_retrieval_topk_few_workspace_bytes(min(m, RETRIEVAL_FEW_MAX), n, d, k), m, n, k, want_sim,
+                                         queries.device)
+    st = _stream()
+    for i in range(0, m, RETRIEVAL_FEW_MAX):  # the calls of a stream run in order: one workspace
+        mm = min(RETRIEVAL_FEW_MAX, m - i)
+        _lib.check(lib.coot_retrieval_topk_few_masked(queries[i:].data_ptr(), gallery.data_ptr(), code, _ptr(norms), _ptr(keep), mm, n, d, k,
+                                                      idx[i:].data_ptr(), scores[i:].data_ptr(), sim[i:].data_ptr() if want_sim else None,
+                                                      ws.data_ptr(), ws.numel(), st), "coot_retrieval_topk_few_masked")
+    return idx, scores, sim
+
+
+def _topk_tile(queries, gallery, norms, k: int, keep, want_sim: bool, method=None, own_keep=None):
+    """coot_retrieval_topk_index: one call for any M.  method, own_keep: name and own filter of GalleryIndex.search (many queries)."""
+    from . import lib as _lib
+    if keep is not None:
+        assert gallery.dim() == 2, gallery.shape
+        keep = _check_keep(method or "retrieval_topk_index_device", keep, gallery.shape[0])
+    mirror = "compute_retrieval_topk" + ("_masked" if method is None and keep is not None else "")
+    detail = None if method else (queries.dtype, queries.shape, gallery.shape)
+    (queries, gallery, norms), code, (m, n, d, k) = _check_search("retrieval_topk_index_device", mirror, queries, gallery, norms, k, detail, method=method)
+    keep = _and_own(own_keep, keep)
+    lib = _lib.load()
+    ws, idx, scores, sim = _topk_buffers(lib.coot_retrieval_topk_index_workspace_bytes(m, n, d, k), m, n, k, want_sim, queries.device)
+    _lib.check(lib.coot_retrieval_topk_index(queries.data_ptr(), gallery.data_ptr(), code, _ptr(norms), _ptr(keep), m, n, d, k, idx.data_ptr(),
+                                             scores.data_ptr(), _ptr(sim), ws.data_ptr(), ws.numel(), _stream()), "coot_retrieval_topk_index")
+    return idx, scores, sim
+
+
+def _topk_grouped(queries, gallery, norms, groups, k: int, num_groups, keep, want_sim: bool, method=None, own_keep=None):
+    """coot_retrieval_topk_grouped for any M: slices of RETRIEVAL_FEW_MAX queries over one workspace.  groups is checked before keep, and
+    keep names the mirror of the filtered search.  method, own_keep: the name and the own filter of GalleryIndex.search_grouped."""
+    import torch
+    from . import lib as _lib
+    fn = "retrieval_topk_grouped_device"
+    assert gallery.dim() == 2, gallery.shape
+    groups = _check_groups(method or fn, groups, gallery.shape[0])
+    if keep is not None:
+        keep = _check_keep(method or fn, keep, gallery.shape[0])
+    queries = queries[None] if queries.dim() == 1 else queries
+    (queries, gallery, norms), code, (m, n, d, k) = _check_search(fn, "compute_retrieval_topk_grouped", queries, gallery, norms, k, method=method)
+    g_total = int(groups.max()) + 1 if num_groups is None else int(num_groups)  # (None: the one synchronisation)
+    if g_total < 1:
+        raise ValueError(f"{fn}: num_groups = {g_total}; there has to be at least one group")
+    keep = _and_own(own_keep, keep)
+    lib = _lib.load()
+    ws, idx, scores, sim = _topk_buffers(lib.coot_retrieval_topk_grouped_workspace_bytes(min(m, RETRIEVAL_FEW_MAX), n, d, k, g_total), m, n, k, want_sim,
+                                         queries.device)
+    group = torch.empty_like(idx)
+    st = _stream()
+    for i in range(0, m, RETRIEVAL_FEW_MAX):  # the calls of a stream run in order: one workspace, its table reset by every call
+        mm = min(RETRIEVAL_FEW_MAX, m - i)
+        _lib.check(lib.coot_retrieval_topk_grouped(queries[i:].data_ptr(), gallery.data_ptr(), code, _ptr(norms), _ptr(keep), groups.data_ptr(), g_total, mm,
+                                                   n, d, k, group[i:].data_ptr(), idx[i:].data_ptr(), scores[i:].data_ptr(),
+                                                   sim[i:].data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(), st), "coot_retrieval_topk_grouped")
+    return group, idx, scores, sim
 
 
 def retrieval_topk_grouped_device(queries, gallery, norms, groups, k: int, num_groups=None, keep=None, want_sim: bool = False):
@@ -353,43 +287,7 @@ def retrieval_topk_grouped_device(queries, gallery, norms, groups, k: int, num_g
     groups left the tail is group -1, idx -1, score -inf.  1 <= k <= min(N, 128), whatever groups and keep hold.
     num_groups=None costs one synchronisation with the device (int(groups.max()) + 1): pass num_groups where it is known.  Otherwise
     nothing synchronises.  More than 16 queries run in slices of 16, one sweep of the gallery each, over one workspace."""
-    import torch
-    from . import lib as _lib
-    fn = "retrieval_topk_grouped_device"
-    assert gallery.dim() == 2, gallery.shape
-    groups = _check_groups(fn, groups, gallery.shape[0])
-    if keep is not None:
-        keep = _check_keep(fn, keep, gallery.shape[0])
-    if not (queries.is_cuda and gallery.is_cuda and (norms is None or norms.is_cuda)):
-        raise RuntimeError(f"{fn} needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk_grouped)")
-    codes = _gallery_codes()
-    if gallery.dtype not in codes:
-        raise ValueError(f"{fn}: a gallery of dtype {gallery.dtype}; it has to be {_STORAGE_NAMES}")
-    if queries.dim() == 1:
-        queries = queries[None]
-    assert queries.dtype == torch.float32 and queries.dim() == 2, (queries.dtype, queries.shape)
-    (m, d), n, k = queries.shape, gallery.shape[0], int(k)
-    if gallery.shape[1] != d:
-        raise ValueError(f"{fn}: queries of width {d}, gallery of width {gallery.shape[1]}")
-    if not 1 <= k <= min(n, 128):
-        raise ValueError(f"{fn}: k = {k} is outside 1 .. min(N = {n}, 128)")
-    assert norms is None or (norms.dtype == torch.float32 and tuple(norms.shape) == (n,)), (norms.dtype, norms.shape, n)
-    g_total = int(groups.max()) + 1 if num_groups is None else int(num_groups)  # (None: the one synchronisation)
-    if g_total < 1:
-        raise ValueError(f"{fn}: num_groups = {g_total}; there has to be at least one group")
-    queries, gallery, norms = queries.contiguous(), gallery.contiguous(), None if norms is None else norms.contiguous()
-    lib = _lib.load()
-    ws, idx, scores, sim = _topk_buffers(lib.coot_retrieval_topk_grouped_workspace_bytes(min(m, RETRIEVAL_FEW_MAX), n, d, k, g_total), m, n, k, want_sim,
-                                         queries.device)
-    group = torch.empty_like(idx)
-    st = torch.cuda.current_stream().cuda_stream
-    for i in range(0, m, RETRIEVAL_FEW_MAX):  # the calls of a stream run in order: one workspace, its table reset by every call
-        mm = min(RETRIEVAL_FEW_MAX, m - i)
-        _lib.check(lib.coot_retrieval_topk_grouped(queries[i:].data_ptr(), gallery.data_ptr(), codes[gallery.dtype], None if norms is None else norms.data_ptr(),
-                                                   None if keep is None else keep.data_ptr(), groups.data_ptr(), g_total, mm, n, d, k, group[i:].data_ptr(),
-                                                   idx[i:].data_ptr(), scores[i:].data_ptr(), sim[i:].data_ptr() if want_sim else None, ws.data_ptr(),
-                                                   ws.numel(), st), "coot_retrieval_topk_grouped")
-    return group, idx, scores, sim
+    return _topk_grouped(queries, gallery, norms, groups, k, num_groups, keep, want_sim)
 
 
 # retrieval_topk_multi_device: the table best [M][G] of one library call holds at most this many entries (2^25 x 8 bytes = 256 MiB); a
@@ -427,27 +325,22 @@ def retrieval_topk_multi_device(queries, offsets, gallery, norms, groups, k: int
     (int(groups.max()) + 1): pass num_groups where it is known.  Every 16 sentences are one sweep of the gallery into a table of M x
     num_groups entries of 8 bytes; above MULTI_TABLE_ENTRIES entries the search runs as several library calls, split where a paragraph
     ends (paragraphs are independent: the same bytes), and one paragraph above 2^28 entries is refused."""
+    return _topk_multi(queries, offsets, gallery, norms, groups, k, num_groups, keep, want_sim)
+
+
+def _topk_multi(queries, offsets, gallery, norms, groups, k: int, num_groups, keep, want_sim: bool, method=None, own_keep=None):
+    """coot_retrieval_topk_multi: the calls _multi_calls cuts, over one workspace.  method, own_keep: those of GalleryIndex.search_multi."""
     import torch
     from . import lib as _lib
     fn = "retrieval_topk_multi_device"
     assert gallery.dim() == 2, gallery.shape
-    groups = _check_groups(fn, groups, gallery.shape[0], mirror=None)  # types and shapes of all three first, then where they live
+    groups = _check_groups(method or fn, groups, gallery.shape[0], mirror=None)  # types and shapes of all three first, then where they live
     if keep is not None:
-        keep = _check_keep(fn, keep, gallery.shape[0], mirror=None)
+        keep = _check_keep(method or fn, keep, gallery.shape[0], mirror=None)
     assert queries.dim() == 2, queries.shape
-    off = _host_offsets(fn, offsets, queries.shape[0])
-    if not (queries.is_cuda and gallery.is_cuda and groups.is_cuda and (keep is None or keep.is_cuda) and (norms is None or norms.is_cuda)):
-        raise RuntimeError(f"{fn} needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk_multi)")
-    codes = _gallery_codes()
-    if gallery.dtype not in codes:
-        raise ValueError(f"{fn}: a gallery of dtype {gallery.dtype}; it has to be {_STORAGE_NAMES}")
-    assert queries.dtype == torch.float32, queries.dtype
-    (m, d), n, k = queries.shape, gallery.shape[0], int(k)
-    if gallery.shape[1] != d:
-        raise ValueError(f"{fn}: queries of width {d}, gallery of width {gallery.shape[1]}")
-    if not 1 <= k <= min(n, 128):
-        raise ValueError(f"{fn}: k = {k} is outside 1 .. min(N = {n}, 128)")
-    assert norms is None or (norms.dtype == torch.float32 and tuple(norms.shape) == (n,)), (norms.dtype, norms.shape, n)
+    off = _host_offsets(method or fn, offsets, queries.shape[0])
+    (queries, gallery, norms), code, (m, n, d, k) = _check_search(fn, "compute_retrieval_topk_multi", queries, gallery, norms, k, queries.dtype,
+                                                                  also=(groups, keep), method=method)
     g_total = int(groups.max()) + 1 if num_groups is None else int(num_groups)  # (None: the one synchronisation)
     if g_total < 1:
         raise ValueError(f"{fn}: num_groups = {g_total}; there has to be at least one group")
@@ -455,7 +348,7 @@ def retrieval_topk_multi_device(queries, offsets, gallery, norms, groups, k: int
     if longest * g_total > MULTI_TABLE_ENTRIES_MAX:
         raise ValueError(f"{fn}: a paragraph of {longest} sentences against {g_total} groups is a table of {longest * g_total} entries; "
                          f"one paragraph has at most 2^28")
-    queries, gallery, norms = queries.contiguous(), gallery.contiguous(), None if norms is None else norms.contiguous()
+    keep = _and_own(own_keep, keep)
     dev, p_total = queries.device, len(off) - 1
     group = torch.empty(p_total, k, dtype=torch.int32, device=dev)
     scores = torch.empty(p_total, k, dtype=torch.float32, device=dev)
@@ -469,7 +362,7 @@ def retrieval_topk_multi_device(queries, offsets, gallery, norms, groups, k: int
     dev_off = torch.from_numpy(rebased).to(dev)
     ws = torch.empty(max(lib.coot_retrieval_topk_multi_workspace_bytes(p1 - p0, int(off[p1] - off[p0]), n, d, k, g_total) for p0, p1 in calls),
                      dtype=torch.uint8, device=dev)
-    st = torch.cuda.current_stream().cuda_stream
+    st = _stream()
     nxt = 0
     for p0, p1 in calls:  # the calls of a stream run in order: one workspace, its table reset by every call
         i0, mm = int(off[p0]), int(off[p1] - off[p0])
@@ -478,10 +371,10 @@ def retrieval_topk_multi_device(queries, offsets, gallery, norms, groups, k: int
             group[p0:p1] = -1
             scores[p0:p1] = float("-inf")
             continue
-        _lib.check(lib.coot_retrieval_topk_multi(queries[i0:].data_ptr(), gallery.data_ptr(), codes[gallery.dtype], None if norms is None else norms.data_ptr(),
-                                                 None if keep is None else keep.data_ptr(), groups.data_ptr(), g_total, dev_off[at:].data_ptr(), p1 - p0, mm,
-                                                 n, d, k, group[p0:].data_ptr(), scores[p0:].data_ptr(), rows[i0:].data_ptr(), row_scores[i0:].data_ptr(),
-                                                 sim[i0:].data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(), st), "coot_retrieval_topk_multi")
+        _lib.check(lib.coot_retrieval_topk_multi(queries[i0:].data_ptr(), gallery.data_ptr(), code, _ptr(norms), _ptr(keep), groups.data_ptr(), g_total,
+                                                 dev_off[at:].data_ptr(), p1 - p0, mm, n, d, k, group[p0:].data_ptr(), scores[p0:].data_ptr(),
+                                                 rows[i0:].data_ptr(), row_scores[i0:].data_ptr(), sim[i0:].data_ptr() if want_sim else None,
+                                                 ws.data_ptr(), ws.numel(), st), "coot_retrieval_topk_multi")
     return group, scores, rows, row_scores, sim
 
 
@@ -580,7 +473,7 @@ class GalleryIndex:
         if self.normalize:
             self._nbuf = torch.empty(self.capacity, dtype=torch.float32, device=gallery.device)
             self.norms = self._nbuf[:n]
-            st = torch.cuda.current_stream().cuda_stream
+            st = _stream()
             if self._code:
                 _lib.check(_lib.load().coot_retrieval_row_norms_h(self.gallery.data_ptr(), self._code, n, d, self.norms.data_ptr(), st),
                            "coot_retrieval_row_norms_h")
@@ -656,12 +549,10 @@ class GalleryIndex:
         return values.contiguous()
 
     def _put(self, values, dest, row0: int, n_rows: int):
-        import torch
         from . import lib as _lib
-        _lib.check(_lib.load().coot_retrieval_rows_put(values.data_ptr(), _gallery_codes()[values.dtype], values.shape[0], values.shape[1],
-                                                       None if dest is None else dest.data_ptr(), row0, self._buf.data_ptr(), self._code, n_rows,
-                                                       self._nbuf.data_ptr() if self.norms is not None else None,
-                                                       torch.cuda.current_stream().cuda_stream), "coot_retrieval_rows_put")
+        _lib.check(_lib.load().coot_retrieval_rows_put(values.data_ptr(), _gallery_codes()[values.dtype], values.shape[0], values.shape[1], _ptr(dest),
+                                                       row0, self._buf.data_ptr(), self._code, n_rows,
+                                                       self._nbuf.data_ptr() if self.norms is not None else None, _stream()), "coot_retrieval_rows_put")
 
     def add(self, rows) -> int:
         """Appends rows (cuda float32 or index.storage, [R, d] or [d]) as gallery rows n .. n + R - 1 and returns the first new row
@@ -759,39 +650,10 @@ class GalleryIndex:
             self._row_flags("restore", rows)  # (nothing is removed: the rows are checked all the same)
 
     def search(self, queries, k: int, want_sim: bool = False, keep=None):
-        import torch
-        from . import lib as _lib
-        if keep is not None:
-            keep = _check_keep("GalleryIndex.search", keep, self.gallery.shape[0])
-        if not queries.is_cuda:
-            raise RuntimeError("GalleryIndex.search needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk)")
-        if queries.dim() == 1:
-            queries = queries[None]
-        (n, d), k = self.gallery.shape, int(k)
-        assert queries.dtype == torch.float32 and queries.dim() == 2, (queries.dtype, queries.shape)
-        if queries.shape[1] != d:
-            raise ValueError(f"GalleryIndex.search: queries of width {queries.shape[1]}, gallery of width {d}")
-        if not 1 <= k <= min(n, 128):
-            raise ValueError(f"GalleryIndex.search: k = {k} is outside 1 .. min(N = {n}, 128)")
-        m = queries.shape[0]
-        if self.keep is not None:  # the index's own filter AND the search's
-            keep = self.keep.view(torch.uint8) if keep is None else (self.keep & (keep != 0)).view(torch.uint8)
-        if m > RETRIEVAL_FEW_MAX and (not self._code or m >= INDEX_TILE_MIN_M_16BIT):
-            return retrieval_topk_index_device(queries, self.gallery, self.norms if self.normalize else None, k, keep=keep, want_sim=want_sim)
-        queries = queries.contiguous()
-        lib = _lib.load()
-        ws, idx, scores, sim = _topk_buffers(lib.coot_retrieval_topk_few_workspace_bytes(min(m, RETRIEVAL_FEW_MAX), n, d, k), m, n, k, want_sim,
-                                             queries.device)
-        norms = self.norms.data_ptr() if self.normalize else None
-        st = torch.cuda.current_stream().cuda_stream
-        for i in range(0, m, RETRIEVAL_FEW_MAX):  # one slice unless RETRIEVAL_FEW_MAX < M < INDEX_TILE_MIN_M_16BIT (16-bit storage only); the calls of a stream run in order: one workspace
-            mm = min(RETRIEVAL_FEW_MAX, m - i)
-            _lib.check(lib.coot_retrieval_topk_few_masked(queries[i:].data_ptr(), self.gallery.data_ptr(), self._code, norms,
-                                                          None if keep is None else keep.data_ptr(), mm, n, d, k, idx[i:].data_ptr(),
-                                                          scores[i:].data_ptr(), sim[i:].data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(), st),
-                       "coot_retrieval_topk_few_masked")
-        return idx, scores, sim
-
+        m = queries.shape[0] if queries.dim() == 2 else 1
+        if m <= RETRIEVAL_FEW_MAX or (self._code and m < INDEX_TILE_MIN_M_16BIT):  # one few-query call, or slices of them (16-bit index)
+            return _topk_few(self, queries, k, keep, want_sim)
+        return _topk_tile(queries, self.gallery, self.norms if self.normalize else None, k, keep, want_sim, method="GalleryIndex.search", own_keep=self.keep)
 
     def search_grouped(self, queries, k: int, groups, num_groups=None, keep=None, want_sim: bool = False):
         """The k best GROUPS of rows for every query, each through its best row: (group int32 [M, k], idx int32 [M, k], scores float32
@@ -804,25 +666,8 @@ class GalleryIndex:
         The index does not store groups; the caller owns the row-to-group table: after add() append to it, after compact() remap it
         with the old row numbers compact returns (groups[old_rows]).  Any M: slices of 16 queries, one sweep of the gallery each
         (retrieval_topk_grouped_device)."""
-        import torch
-        fn = "GalleryIndex.search_grouped"
-        groups = _check_groups(fn, groups, self.gallery.shape[0])
-        if keep is not None:
-            keep = _check_keep(fn, keep, self.gallery.shape[0])
-        if not queries.is_cuda:
-            raise RuntimeError(f"{fn} needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk_grouped)")
-        if queries.dim() == 1:
-            queries = queries[None]
-        (n, d), k = self.gallery.shape, int(k)
-        assert queries.dtype == torch.float32 and queries.dim() == 2, (queries.dtype, queries.shape)
-        if queries.shape[1] != d:
-            raise ValueError(f"{fn}: queries of width {queries.shape[1]}, gallery of width {d}")
-        if not 1 <= k <= min(n, 128):
-            raise ValueError(f"{fn}: k = {k} is outside 1 .. min(N = {n}, 128)")
-        if self.keep is not None:  # the index's own filter AND the search's
-            keep = self.keep if keep is None else self.keep & (keep != 0)
-        return retrieval_topk_grouped_device(queries, self.gallery, self.norms if self.normalize else None, groups, k, num_groups=num_groups, keep=keep,
-                                             want_sim=want_sim)
+        return _topk_grouped(queries, self.gallery, self.norms if self.normalize else None, groups, k, num_groups, keep, want_sim,
+                             method="GalleryIndex.search_grouped", own_keep=self.keep)
 
     def search_multi(self, queries, offsets, k: int, groups, num_groups=None, keep=None, want_sim: bool = False):
         """The k best GROUPS of rows for every PARAGRAPH of queries, and which row answers each sentence (MaxSim, late interaction):
@@ -836,75 +681,8 @@ class GalleryIndex:
         compute_retrieval_topk_multi of the similarities search() selects from, byte for byte.  keep and the index's own filter (remove)
         combine as in search.  1 <= k <= min(N, 128).  num_groups=None costs one synchronisation; the caller owns the row-to-group
         table, as in search_grouped.  Any M: 16 sentences are one sweep of the gallery (retrieval_topk_multi_device)."""
-        fn = "GalleryIndex.search_multi"
-        groups = _check_groups(fn, groups, self.gallery.shape[0], mirror=None)
-        if keep is not None:
-            keep = _check_keep(fn, keep, self.gallery.shape[0], mirror=None)
-        assert queries.dim() == 2, queries.shape
-        _host_offsets(fn, offsets, queries.shape[0])
-        if not (queries.is_cuda and groups.is_cuda and (keep is None or keep.is_cuda)):
-            raise RuntimeError(f"{fn} needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk_multi)")
-        (n, d), k = self.gallery.shape, int(k)
-        if queries.shape[1] != d:
-            raise ValueError(f"{fn}: queries of width {queries.shape[1]}, gallery of width {d}")
-        if not 1 <= k <= min(n, 128):
-            raise ValueError(f"{fn}: k = {k} is outside 1 .. min(N = {n}, 128)")
-        if self.keep is not None:  # the index's own filter AND the search's
-            keep = self.keep if keep is None else self.keep & (keep != 0)
-        return retrieval_topk_multi_device(queries, offsets, self.gallery, self.norms if self.normalize else None, groups, k, num_groups=num_groups,
-                                           keep=keep, want_sim=want_sim)
-
-
-def _ahead(s, idx, t, a):
-    """The device tie rule: entry (s, idx) is ahead of (t, a) when it is larger, or equal with a later index."""
-    return (s > t) | ((s == t) & (idx > a))
-
-
-def _labeled_metrics(ranks: np.ndarray) -> Tuple[Dict[str, float], np.ndarray]:
-    """The seven metrics over the entries >= 0 of a rank vector, in the fp32 / fp64 steps of the device kernel, as a dictionary
-    and as the float32 [7] the device writes (n == 0: zeros)."""
-    r = ranks[ranks >= 0].astype(np.int64)
-    n = len(r)
-    out = np.zeros(7, np.float32)
-    if n:
-        nf = np.float32(n)
-        r1, r5, r10, r50 = [np.float32((r < k).sum()) / nf for k in (1, 5, 10, 50)]
-        r = np.sort(r)
-        med = 0.5 * (np.float64(r[(n - 1) // 2]) + np.float64(r[n // 2]))
-        out[:] = [r1, r5, r10, r50, np.float32(np.floor(med) + 1.0), np.float32(np.float64(r.sum()) / np.float64(n) + 1.0), (r1 + r5) + r50]
-    return {k: float(v) for k, v in zip(VALKEYS, out)}, out
-
-
-def compute_retrieval_labeled(sim: np.ndarray, labels: np.ndarray):
-    """Host mirror of coot_retrieval_ranks_labeled on a similarity matrix sim [M, N] (queries x gallery): labels[i] is the gallery
-    row of query i; a label outside [0, N) means "no ground truth" (rank -1, in neither direction's ranks or metrics).  Returns
-    (res_q2g, res_g2q, ranks_q int32 [M], ranks_g int32 [N]).
-    ranks_q[i] = the entries (s[i, j], j), j != g, ahead of (s[i, g], g), g = labels[i]: the position of g in
-    np.argsort(sim[i], kind="stable")[::-1].  ranks_g[j] = the entries (s[i', j], i') of column j ahead of the column's best
-    positive, the query with labels[i] == j that is ahead of the other ones: the minimum over the column's ground-truth queries of
-    their position in np.argsort(sim[:, j], kind="stable")[::-1]; -1 for gallery rows without a valid query.  The metric
-    dictionaries (VALKEYS) are taken over the valid entries of each direction (n == 0: zeros)."""
-    sim = np.asarray(sim)
-    labels = np.asarray(labels).astype(np.int64).reshape(-1)
-    m, n = sim.shape
-    assert labels.shape == (m,), (sim.shape, labels.shape)
-    valid = (labels >= 0) & (labels < n)
-    ranks_q, ranks_g = np.full(m, -1, np.int32), np.full(n, -1, np.int32)
-    cols = np.arange(n)
-    for i in np.nonzero(valid)[0]:
-        g = labels[i]
-        ranks_q[i] = ((cols != g) & _ahead(sim[i], cols, sim[i, g], g)).sum()
-    rows = np.arange(m)
-    for j in np.unique(labels[valid]):
-        col = sim[:, j]
-        t, a = None, -1
-        for i in np.nonzero(valid & (labels == j))[0]:  # ascending i: an equal score with a later index is ahead
-            if t is None or col[i] >= t:
-                t, a = col[i], i
-        ranks_g[j] = _ahead(col, rows, t, a).sum()
-    res_q, _ = _labeled_metrics(ranks_q)
-    res_g, _ = _labeled_metrics(ranks_g)
-    return res_q, res_g, ranks_q, ranks_g
+        return _topk_multi(queries, offsets, self.gallery, self.norms if self.normalize else None, groups, k, num_groups, keep, want_sim,
+                           method="GalleryIndex.search_multi", own_keep=self.keep)
 
 
 def retrieval_ranks_labeled_device(queries, gallery, labels, normalize: bool = False, want_sim: bool = False):
@@ -914,8 +692,7 @@ def retrieval_ranks_labeled_device(queries, gallery, labels, normalize: bool = F
     import torch
     from . import lib as _lib
     queries, gallery = _device_pair("retrieval_ranks_labeled_device", "compute_retrieval_labeled", queries, gallery, torch.float32, same_shape=False)
-    if not labels.is_cuda:
-        raise RuntimeError("retrieval_ranks_labeled_device needs CUDA tensors (there is no CPU fallback; use compute_retrieval_labeled)")
+    _on_device("retrieval_ranks_labeled_device", "compute_retrieval_labeled", labels)
     (m, d), n = queries.shape, gallery.shape[0]
     assert labels.dtype == torch.int32 and labels.shape == (m,), (labels.dtype, labels.shape, m)
     labels = labels.contiguous()
@@ -928,47 +705,23 @@ def retrieval_ranks_labeled_device(queries, gallery, labels, normalize: bool = F
     met = torch.empty(2, 7, dtype=torch.float32, device=dev)
     sim = torch.empty(m, n, dtype=torch.float32, device=dev) if want_sim else None
     _lib.check(lib.coot_retrieval_ranks_labeled(queries.data_ptr(), gallery.data_ptr(), labels.data_ptr(), m, n, d, int(normalize),
-                                                ranks_q.data_ptr(), ranks_g.data_ptr(), n_valid.data_ptr(), met.data_ptr(),
-                                                sim.data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(),
-                                                torch.cuda.current_stream().cuda_stream), "coot_retrieval_ranks_labeled")
+                                                ranks_q.data_ptr(), ranks_g.data_ptr(), n_valid.data_ptr(), met.data_ptr(), _ptr(sim), ws.data_ptr(),
+                                                ws.numel(), _stream()), "coot_retrieval_ranks_labeled")
     return ranks_q, ranks_g, n_valid, met, sim
 
 
-def compute_retrieval_labeled_device(queries, gallery, labels, normalize: bool = False):
-    """Device version of compute_retrieval_labeled for embeddings (not a similarity matrix): (res_q2g, res_g2q, sum_at_1) with the
-    reference's dictionary keys, as compute_retrieval_device returns them.  One 56-byte D2H copy."""
-    met = retrieval_ranks_labeled_device(queries, gallery, labels, normalize)[3]
+def _metric_dicts(met):
+    """(res_1to2, res_2to1, sum_at_1) with the reference's dictionary keys, from the device's metrics [2, 7]: the one 56-byte D2H copy."""
     m = met.cpu().numpy().astype(np.float64)
     res1 = {k: float(v) for k, v in zip(VALKEYS, m[0])}
     res2 = {k: float(v) for k, v in zip(VALKEYS, m[1])}
     return res1, res2, (res1["r1"] + res2["r1"]) / 2
 
 
-def strip_bounds(n: int, world: int, rank: int) -> Tuple[int, int]:
-    """(row0, rows) of rank's strip of n rows: an even split over the ranks, the remainder to the first ranks."""
-    base, rem = divmod(int(n), int(world))
-    return rank * base + min(rank, rem), base + (1 if rank < rem else 0)
-
-
-def compute_retrieval_counts_part(sim: np.ndarray, row0: int, rows: int) -> Tuple[np.ndarray, np.ndarray]:
-    """Host mirror of coot_retrieval_ranks_part on a similarity matrix sim [N, N]: (counts_12, counts_21) int32 [N] of the strip
-    of rows [row0, row0 + rows).  counts_12[i] = the entries of row i ahead of sim[i, i] (strip rows only, 0 elsewhere),
-    counts_21[j] = the strip's entries of column j ahead of sim[j, j]; "ahead" = larger, or equal with a later index (the device
-    tie rule).  Summed over the strips of any partition of [0, N) they are the two rank vectors."""
-    sim = np.asarray(sim)
-    n = sim.shape[0]
-    assert sim.shape == (n, n) and 0 <= row0 and 0 <= rows and row0 + rows <= n, (sim.shape, row0, rows)
-    c12, c21 = np.zeros(n, np.int32), np.zeros(n, np.int32)
-    if rows == 0:
-        return c12, c21
-    diag = np.diagonal(sim)
-    s = sim[row0:row0 + rows]
-    i, j = np.arange(row0, row0 + rows)[:, None], np.arange(n)[None, :]
-    di, dj = diag[row0:row0 + rows, None], diag[None, :]
-    off = i != j
-    c12[row0:row0 + rows] = (off & ((s > di) | ((s == di) & (j > i)))).sum(axis=1)
-    c21[:] = (off & ((s > dj) | ((s == dj) & (i > j)))).sum(axis=0)
-    return c12, c21
+def compute_retrieval_labeled_device(queries, gallery, labels, normalize: bool = False):
+    """Device version of compute_retrieval_labeled for embeddings (not a similarity matrix): (res_q2g, res_g2q, sum_at_1) with the
+    reference's dictionary keys, as compute_retrieval_device returns them.  One 56-byte D2H copy."""
+    return _metric_dicts(retrieval_ranks_labeled_device(queries, gallery, labels, normalize)[3])
 
 
 def retrieval_ranks_part_device(emb1, emb2, row0: int, rows: int, normalize: bool = False, want_sim: bool = False):
@@ -987,8 +740,7 @@ def retrieval_ranks_part_device(emb1, emb2, row0: int, rows: int, normalize: boo
     counts = torch.empty(2, n, dtype=torch.int32, device=emb1.device)
     sim = torch.empty(rows, n, dtype=torch.float32, device=emb1.device) if want_sim else None
     _lib.check(lib.coot_retrieval_ranks_part(emb1.data_ptr(), emb2.data_ptr(), n, d, int(normalize), row0, rows, counts[0].data_ptr(),
-                                             counts[1].data_ptr(), sim.data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(),
-                                             torch.cuda.current_stream().cuda_stream), "coot_retrieval_ranks_part")
+                                             counts[1].data_ptr(), _ptr(sim), ws.data_ptr(), ws.numel(), _stream()), "coot_retrieval_ranks_part")
     return counts, sim
 
 
@@ -1002,7 +754,7 @@ def retrieval_metrics_device(ranks_12, ranks_21):
     hist = torch.empty(2 * n, dtype=torch.int32, device=ranks_12.device)
     met = torch.empty(2, 7, dtype=torch.float32, device=ranks_12.device)
     _lib.check(_lib.load().coot_retrieval_metrics(ranks_12.data_ptr(), ranks_21.data_ptr(), n, met.data_ptr(), hist.data_ptr(), hist.numel() * 4,
-                                                  torch.cuda.current_stream().cuda_stream), "coot_retrieval_metrics")
+                                                  _stream()), "coot_retrieval_metrics")
     return met
 
 
@@ -1017,8 +769,4 @@ def compute_retrieval_device(emb1, emb2, normalize: bool = False, dp=None):
     counts, _ = retrieval_ranks_part_device(emb1, emb2, row0, rows, normalize)
     if W > 1:
         dp.all_reduce_sum(counts)
-    met = retrieval_metrics_device(counts[0], counts[1])
-    m = met.cpu().numpy().astype(np.float64)
-    res1 = {k: float(v) for k, v in zip(VALKEYS, m[0])}
-    res2 = {k: float(v) for k, v in zip(VALKEYS, m[1])}
-    return res1, res2, (res1["r1"] + res2["r1"]) / 2
+    return _metric_dicts(retrieval_metrics_device(counts[0], counts[1]))
