@@ -13,9 +13,11 @@ row that the selection consults (compute_retrieval_topk_masked).  One library ca
 coot_retrieval_topk_index (tile, on an index), coot_retrieval_topk_few_masked (few queries, any storage).
 retrieval_topk_grouped_device / GalleryIndex.search_grouped: the K best GROUPS of gallery rows, each through its best row
 (compute_retrieval_topk_grouped): coot_retrieval_topk_grouped.  retrieval_topk_multi_device / GalleryIndex.search_multi: the K best
-groups for a PARAGRAPH of queries (compute_retrieval_topk_multi): coot_retrieval_topk_multi.
+groups for a PARAGRAPH of queries (compute_retrieval_topk_multi): coot_retrieval_topk_multi.  retrieval_topk_scoped_device /
+GalleryIndex.search_scoped: every query inside (only=) or outside (exclude=) the rows with the id it brings
+(compute_retrieval_topk_scoped): coot_retrieval_topk_scoped; GalleryIndex.neighbors: a row's neighbours outside its own group.
 The searches on a prepared gallery share one host check (_check_search) and have one implementation per library call (_topk_few,
-_topk_tile, _topk_grouped, _topk_multi), which the public wrapper and the GalleryIndex method both call.
+_topk_tile, _topk_grouped, _topk_multi, _topk_scoped), which the public wrapper and the GalleryIndex method both call.
 GalleryIndex.add / update / compact: rows appended or overwritten in place together with their norms (coot_retrieval_rows_put),
 removed rows dropped — the index then holds, byte for byte, what a fresh index on the same rows holds.
 
@@ -28,7 +30,7 @@ import numpy as np
 
 from .retrieval_mirror import (VALKEYS, _ahead, _host_offsets, _labeled_metrics, compute_retrieval, compute_retrieval_cosine,  # noqa: F401
                                compute_retrieval_counts_part, compute_retrieval_labeled, compute_retrieval_topk, compute_retrieval_topk_grouped,
-                               compute_retrieval_topk_masked, compute_retrieval_topk_multi, strip_bounds)
+                               compute_retrieval_topk_masked, compute_retrieval_topk_multi, compute_retrieval_topk_scoped, strip_bounds)
 
 
 def _ptr(t):
@@ -288,6 +290,86 @@ def retrieval_topk_grouped_device(queries, gallery, norms, groups, k: int, num_g
     num_groups=None costs one synchronisation with the device (int(groups.max()) + 1): pass num_groups where it is known.  Otherwise
     nothing synchronises.  More than 16 queries run in slices of 16, one sweep of the gallery each, over one workspace."""
     return _topk_grouped(queries, gallery, norms, groups, k, num_groups, keep, want_sim)
+
+
+def _check_scope(fn: str, only, exclude, m: int):
+    """The scope of a scoped search, checked on the host before anything is launched: exactly one of only / exclude (ValueError), one
+    id per query: a cuda torch.int32 or torch.int64 tensor [M], or ids on the host (a sequence, a numpy array or a CPU tensor of
+    integers inside int32) that the caller uploads once.  Returns (the cuda tensor or an int32 numpy array, exclude as 0 / 1)."""
+    import torch
+    if (only is None) == (exclude is None):
+        raise ValueError(f"{fn}: exactly one of only= and exclude= has to be given, not {'both' if only is not None else 'neither'}")
+    scope, name = (exclude, "exclude") if only is None else (only, "only")
+    if isinstance(scope, torch.Tensor) and scope.is_cuda:
+        if scope.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"{fn}: {name} has to hold integers (torch.int32 or torch.int64 on the device), not {scope.dtype}")
+        shape = tuple(scope.shape)
+    else:
+        try:
+            scope = np.asarray(scope.numpy() if isinstance(scope, torch.Tensor) else scope)
+        except Exception:
+            scope = np.asarray(None)
+        if scope.dtype.kind not in "iu":
+            raise ValueError(f"{fn}: {name} has to hold integers (one id per query), not dtype {scope.dtype}")
+        shape = scope.shape
+    if shape != (m,):
+        raise ValueError(f"{fn}: {name} of shape {tuple(shape)}, {m} queries (one id per query: [{m}])")
+    if isinstance(scope, np.ndarray):
+        if scope.size and (scope.min() < -2 ** 31 or scope.max() > 2 ** 31 - 1):
+            raise ValueError(f"{fn}: {name} holds an id outside int32, which no row carries")
+        scope = np.ascontiguousarray(scope.astype(np.int32))
+    return scope, int(only is None)
+
+
+def _topk_scoped(queries, gallery, norms, groups, k: int, only, exclude, keep, want_sim: bool, method=None, own_keep=None):
+    """coot_retrieval_topk_scoped for any M: slices of RETRIEVAL_FEW_MAX queries, each with its slice of the scope, over one workspace.
+    Checked in this order: only / exclude, groups, keep, the scope's type and shape, then where everything lives.  method, own_keep: the
+    name and the own filter of GalleryIndex.search_scoped / neighbors."""
+    import torch
+    from . import lib as _lib
+    fn = "retrieval_topk_scoped_device"
+    who = method or fn
+    if (only is None) == (exclude is None):
+        _check_scope(who, only, exclude, 0)
+    assert gallery.dim() == 2, gallery.shape
+    if groups is not None:
+        groups = _check_groups(who, groups, gallery.shape[0], mirror=None)
+    if keep is not None:
+        keep = _check_keep(who, keep, gallery.shape[0], mirror=None)
+    queries = queries[None] if queries.dim() == 1 else queries
+    assert queries.dim() == 2, queries.shape
+    scope, excl = _check_scope(who, only, exclude, queries.shape[0])
+    (queries, gallery, norms), code, (m, n, d, k) = _check_search(fn, "compute_retrieval_topk_scoped", queries, gallery, norms, k, queries.dtype,
+                                                                  also=(groups, keep), method=method)
+    scope = torch.from_numpy(scope).to(queries.device) if isinstance(scope, np.ndarray) else scope.to(torch.int32).contiguous()
+    keep = _and_own(own_keep, keep)
+    lib = _lib.load()
+    ws, idx, scores, sim = _topk_buffers(lib.coot_retrieval_topk_scoped_workspace_bytes(min(m, RETRIEVAL_FEW_MAX), n, d, k), m, n, k, want_sim,
+                                         queries.device)
+    st = _stream()
+    for i in range(0, m, RETRIEVAL_FEW_MAX):  # the calls of a stream run in order: one workspace
+        mm = min(RETRIEVAL_FEW_MAX, m - i)
+        _lib.check(lib.coot_retrieval_topk_scoped(queries[i:].data_ptr(), gallery.data_ptr(), code, _ptr(norms), _ptr(keep), _ptr(groups),
+                                                  scope[i:].data_ptr(), excl, mm, n, d, k, idx[i:].data_ptr(), scores[i:].data_ptr(),
+                                                  sim[i:].data_ptr() if want_sim else None, ws.data_ptr(), ws.numel(), st), "coot_retrieval_topk_scoped")
+    return idx, scores, sim
+
+
+def retrieval_topk_scoped_device(queries, gallery, norms, groups, k: int, only=None, exclude=None, keep=None, want_sim: bool = False):
+    """The scoped search on a gallery as a prepared index holds it (coot_retrieval_topk_scoped): every query has its own slice of the
+    gallery.  queries cuda float32 [M, d], gallery cuda float32, bfloat16 or float16 [N, d], norms cuda float32 [N] (GalleryIndex.norms)
+    or None: rows used as they are; groups cuda torch.int32 or torch.int64 [N] (int64 is converted once), groups[j] = the id of gallery
+    row j, any int32 value, or None: every row is its own id (groups[j] = j).  Exactly one of only= / exclude= (both or neither:
+    ValueError): one id per query, [M], a cuda torch.int32 or torch.int64 tensor, or a host sequence, numpy array or CPU tensor of
+    integers, which is uploaded once.  Row j is eligible for query i when keep lets it pass and groups[j] == only[i] (within one video:
+    which clip of it answers the sentence), or groups[j] != exclude[i] (everything but one video).  Returns (idx int32 [M, k], scores
+    float32 [M, k], sim [M, N] or None) on the device: row i is, byte for byte, GalleryIndex.search(queries[i:i + 1], k,
+    keep=eligible_i) — compute_retrieval_topk_scoped of the similarities the other searches select from, without M masks, M calls and M
+    sweeps.  An id that no row carries selects nothing under only and excludes nothing under exclude; with fewer than k eligible rows
+    the tail is idx -1, score -inf.  1 <= k <= min(N, 128), whatever the scopes and keep hold.  sim holds every similarity, eligible
+    or not; without it, blocks of 128 rows in which no row is eligible for any query of a slice are not read.  Nothing synchronises.
+    More than 16 queries run in slices of 16, one sweep of the gallery each, over one workspace."""
+    return _topk_scoped(queries, gallery, norms, groups, k, only, exclude, keep, want_sim)
 
 
 # retrieval_topk_multi_device: the table best [M][G] of one library call holds at most this many entries (2^25 x 8 bytes = 256 MiB); a
@@ -683,6 +765,49 @@ class GalleryIndex:
         table, as in search_grouped.  Any M: 16 sentences are one sweep of the gallery (retrieval_topk_multi_device)."""
         return _topk_multi(queries, offsets, self.gallery, self.norms if self.normalize else None, groups, k, num_groups, keep, want_sim,
                            method="GalleryIndex.search_multi", own_keep=self.keep)
+
+    def search_scoped(self, queries, k: int, groups, only=None, exclude=None, keep=None, want_sim: bool = False):
+        """The k best rows for every query INSIDE ITS OWN SLICE of the gallery: (idx int32 [M, k], scores float32 [M, k], sim [M, N] or
+        None) on the device.  groups: a cuda torch.int32 or torch.int64 tensor [index.n], groups[j] = the id of gallery row j (the video
+        of a clip, a tenant, a split; any int32 value), or None: every row is its own id.  Exactly one of only= / exclude=, one id per
+        query ([M]; a cuda int tensor, or a host sequence, array or CPU tensor that is uploaded once): with only, query i sees the rows
+        with groups[j] == only[i] — for a sentence and a video, which clip of that video answers it; with exclude, the rows with
+        groups[j] != exclude[i] — everything but one video.  Exact: row i is the bytes of search(queries[i:i + 1], k, keep=eligible_i),
+        compute_retrieval_topk_scoped of the similarities search() selects from, in one sweep per 16 queries instead of one mask, one
+        call and one sweep per query.  An id that no row carries selects nothing under only (the whole row is -1 / -inf) and excludes
+        nothing under exclude; with fewer than k eligible rows the tail is idx -1, score -inf.  keep and the index's own filter
+        (remove) combine as in search.  1 <= k <= min(N, 128).  Without sim, blocks of 128 rows in which no row is eligible for any
+        query of a slice are not read, so only= over adjacent rows costs the blocks those rows lie in.  Nothing synchronises.  The
+        index does not store groups; the caller owns the table across add() and compact(), as in search_grouped."""
+        return _topk_scoped(queries, self.gallery, self.norms if self.normalize else None, groups, k, only, exclude, keep, want_sim,
+                            method="GalleryIndex.search_scoped", own_keep=self.keep)
+
+    def neighbors(self, rows, k: int, groups=None, keep=None):
+        """More like this: the k best rows for each of the index's own rows, (idx int32 [R, k], scores float32 [R, k]) on the device.
+        rows: row numbers, a host sequence or CPU tensor (checked: IndexError outside [0, n)) or a cuda int tensor (not checked: a
+        number outside [0, n) is clamped into it).  The queries are gallery[rows] widened to float32 (exact), and the search is
+        search_scoped(queries, k, groups, exclude=groups[rows], keep=keep): a row never returns its own group — with groups its own
+        video's other clips, with groups=None (every row its own id) just itself.  An exact duplicate of a row elsewhere in the gallery
+        is returned, ahead of everything it ties with by the larger row.  Removed rows may be asked about and are never returned."""
+        import torch
+        n, dev = self.gallery.shape[0], self.gallery.device
+        fn = "GalleryIndex.neighbors"
+        if isinstance(rows, torch.Tensor) and rows.is_cuda:
+            if rows.dtype.is_floating_point or rows.dtype is torch.bool:
+                raise TypeError(f"{fn}: rows of dtype {rows.dtype}; row numbers are integers")
+            r = rows.reshape(-1).to(torch.int64).clamp(0, n - 1)
+        else:
+            r = _host_rows("neighbors", rows, n)
+        if groups is not None:
+            groups = _check_groups(fn, groups, n, mirror=None)
+        if not self.gallery.is_cuda or (groups is not None and not groups.is_cuda):
+            raise RuntimeError(f"{fn} needs CUDA tensors (there is no CPU fallback; use compute_retrieval_topk_scoped)")
+        if isinstance(r, np.ndarray):
+            r = torch.from_numpy(r).to(dev)
+        scope = r.to(torch.int32) if groups is None else groups[r]
+        idx, scores, _ = _topk_scoped(self.gallery[r].float(), self.gallery, self.norms if self.normalize else None, groups, k, None, scope, keep,
+                                      False, method=fn, own_keep=self.keep)
+        return idx, scores
 
 
 def retrieval_ranks_labeled_device(queries, gallery, labels, normalize: bool = False, want_sim: bool = False):

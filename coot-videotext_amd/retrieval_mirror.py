@@ -3,9 +3,10 @@ Nothing here touches the device or imports torch; retrieval.py re-exports every 
 Retrieval metrics, nntrainer/retrieval.py:31-98 semantics: rank of the diagonal item in argsort(row)[::-1]; R@K as
 fractions; medr = floor(median)+1; meanr = mean+1.
 compute_retrieval / compute_retrieval_cosine: mirror of the reference functions, for CPU tensors.
-compute_retrieval_topk (_masked, _grouped, _multi): WHICH gallery items a query retrieves (the reference returns top1 only), on a
-similarity matrix [M, N], M and N independent; under a keep flag per gallery row; the K best GROUPS of rows, each through its best
-row; the K best groups for a PARAGRAPH of queries (MaxSim), whose offsets _host_offsets checks for mirror and device wrappers alike.
+compute_retrieval_topk (_masked, _grouped, _multi, _scoped): WHICH gallery items a query retrieves (the reference returns top1 only),
+on a similarity matrix [M, N], M and N independent; under a keep flag per gallery row; the K best GROUPS of rows, each through its
+best row; the K best groups for a PARAGRAPH of queries (MaxSim), whose offsets _host_offsets checks for mirror and device wrappers
+alike; under a mask per QUERY, the rows with (only) or without (exclude) the id the query brings.
 compute_retrieval_labeled: ranks and metrics without the assumption "square, ground truth on the diagonal": labels[i] = the gallery
 row of query i; several queries per row, rows without a query and queries without a row (a label outside [0, N)) are allowed.
 strip_bounds / compute_retrieval_counts_part: one strip of rows of the sharded validation; the sum over the strips is the whole."""
@@ -95,6 +96,32 @@ def compute_retrieval_topk_grouped(sim: np.ndarray, k: int, groups, num_groups: 
                 group[i, r], idx[i, r], scores[i, r] = groups[j], j, sim[i, j]
                 r += 1
     return group, idx, scores
+
+
+def compute_retrieval_topk_scoped(sim: np.ndarray, k: int, groups, only=None, exclude=None, keep=None) -> Tuple[np.ndarray, np.ndarray]:
+    """compute_retrieval_topk_masked with a mask of its own for every row of sim [M, N]: (idx int32 [M, k], scores [M, k]).  groups
+    [N] integers: groups[j] is the id of column j (None: arange(N), every column its own id).  Exactly one of only / exclude is given,
+    [M] integers, one id per row: column j is eligible for row i when keep[j] != 0 (keep [N] booleans or bytes, None: every column)
+    and groups[j] == only[i], or groups[j] != exclude[i].  Integer equality, nothing else: an id that no column carries selects nothing
+    under only (the whole row is idx -1, score -inf) and excludes nothing under exclude.  1 <= k <= N whatever the scopes hold; with
+    fewer than k eligible columns the tail of a row is idx = -1, score = -inf."""
+    sim = np.asarray(sim)
+    assert sim.ndim == 2, sim.shape
+    m, n = sim.shape
+    assert (only is None) != (exclude is None), "exactly one of only / exclude"
+    groups = np.arange(n) if groups is None else np.asarray(groups).astype(np.int64).reshape(-1)
+    scope = np.asarray(exclude if only is None else only).astype(np.int64).reshape(-1)
+    assert 1 <= k <= n and groups.shape == (n,) and scope.shape == (m,), (sim.shape, k, groups.shape, scope.shape)
+    ok = np.ones(n, bool)
+    if keep is not None:
+        keep = np.asarray(keep)
+        assert keep.shape == (n,), (keep.shape, n)
+        ok = keep != 0
+    idx = np.empty((m, k), np.int32)
+    scores = np.empty((m, k), sim.dtype)
+    for i in range(m):
+        idx[i], scores[i] = compute_retrieval_topk_masked(sim[i:i + 1], k, ok & ((groups == scope[i]) == (only is not None)))
+    return idx, scores
 
 
 def _host_offsets(fn: str, offsets, m: int, exc=ValueError) -> np.ndarray:

@@ -498,6 +498,32 @@ int coot_retrieval_topk_multi(const float* queries, const void* gallery, int gal
                               int32_t* group_out, float* score_out, int32_t* row_out, float* row_score_out, float* sim_out, void* workspace,
                               size_t workspace_bytes, coot_stream_t stream);
 
+/* ---- scoped search: every query has its own slice of the gallery ----------------------------------------------------------------
+ * groups: device int32 [N], groups[j] = the id of gallery row j (the video of a clip, a tenant, a split), any int32 value; NULL: every
+ * row is its own id, groups[j] = j.  scope: device int32 [M], one id per query.  Row j is eligible for query i when it passes keep
+ * (NULL: no filter) and
+ *   exclude == 0 ("only"):    groups[j] == scope[i]  — within one video: which clip of it answers the sentence;
+ *   exclude == 1 ("exclude"): groups[j] != scope[i]  — everything but one video: neighbours outside a clip's own video.
+ * The compare is integer equality: no range and no num_groups.  An id that no row carries selects nothing under only (every slot of
+ * that query is unfilled) and excludes nothing under exclude.  idx_out, score_out [M, K]: row i is, byte for byte, what
+ * coot_retrieval_topk_few_masked returns for query i alone with keep = the flags of its eligible rows: the same fp32 FMA chain, the
+ * same total order (score descending, then the larger row), idx -1 / score -inf in the slots that fewer than K eligible rows leave
+ * unfilled.  sim_out [M, N], optional: every similarity, eligible or not.
+ *   1 <= M <= COOT_RETRIEVAL_FEW_MAX, 1 <= K <= min(N, 128) (K is not checked against the scopes or the mask);
+ *   gallery_dtype COOT_GALLERY_F32, _BF16 or _F16; gallery_norms NULL: rows used as they are.
+ * One sweep of the gallery serves all M queries: the thread of a row forms a 16-bit word, bit i = eligible for query i, which gates
+ * the candidates.  Without sim_out a block of 128 rows in which no row is eligible for any query is not read at all, so under only,
+ * with a scope's rows adjacent, a call reads the blocks those rows lie in; under exclude, or with scattered ids, it reads the gallery
+ * once.  The result does not depend on the sweep's row splits (coot_set_option("rt_few_splits", n)).  workspace (16-byte aligned):
+ * coot_retrieval_topk_scoped_workspace_bytes(M, N, d, K), the few-query search's layout; it needs no device, does not depend on the
+ * option and is 256 for arguments out of range.  A refused call (unknown dtype, null pointer other than gallery_norms, keep, groups and
+ * sim_out, M or K outside its range, exclude not 0 or 1, workspace misaligned or too small) returns before any launch and writes
+ * nothing.  No allocation, no synchronisation; no pointer is retained. */
+size_t coot_retrieval_topk_scoped_workspace_bytes(int M, int N, int d, int K);
+int coot_retrieval_topk_scoped(const float* queries, const void* gallery, int gallery_dtype, const float* gallery_norms, const uint8_t* keep,
+                               const int32_t* groups, const int32_t* scope, int exclude, int M, int N, int d, int K, int32_t* idx_out,
+                               float* score_out, float* sim_out, void* workspace, size_t workspace_bytes, coot_stream_t stream);
+
 /* ---- a prepared gallery that changes: rows written in place, their norms with them ---------------------------------------
  * coot_retrieval_rows_put writes the R rows of src [R, d] into the buffer gallery [N, d] and, where norms != NULL, norms[row] of
  * every row it wrote: what a corpus that grows (rows appended into spare capacity) or is re-encoded (rows overwritten) needs,
