@@ -16,6 +16,8 @@ retrieval_topk_grouped_device / GalleryIndex.search_grouped: the K best GROUPS o
 groups for a PARAGRAPH of queries (compute_retrieval_topk_multi): coot_retrieval_topk_multi.  retrieval_topk_scoped_device /
 GalleryIndex.search_scoped: every query inside (only=) or outside (exclude=) the rows with the id it brings
 (compute_retrieval_topk_scoped): coot_retrieval_topk_scoped; GalleryIndex.neighbors: a row's neighbours outside its own group.
+retrieval_range_device / GalleryIndex.search_range, count_range: every row at or above a query's threshold, however many, as CSR
+(compute_retrieval_range): coot_retrieval_range_count, _scan, _fill (_range).
 The searches on a prepared gallery share one host check (_check_search) and have one implementation per library call (_topk_few,
 _topk_tile, _topk_grouped, _topk_multi, _topk_scoped), which the public wrapper and the GalleryIndex method both call.
 GalleryIndex.add / update / compact: rows appended or overwritten in place together with their norms (coot_retrieval_rows_put),
@@ -30,7 +32,8 @@ import numpy as np
 
 from .retrieval_mirror import (VALKEYS, _ahead, _host_offsets, _labeled_metrics, compute_retrieval, compute_retrieval_cosine,  # noqa: F401
                                compute_retrieval_counts_part, compute_retrieval_labeled, compute_retrieval_topk, compute_retrieval_topk_grouped,
-                               compute_retrieval_topk_masked, compute_retrieval_topk_multi, compute_retrieval_topk_scoped, strip_bounds)
+                               compute_retrieval_range, compute_retrieval_topk_masked, compute_retrieval_topk_multi, compute_retrieval_topk_scoped,
+                               strip_bounds)
 
 
 def _ptr(t):
@@ -372,6 +375,126 @@ def retrieval_topk_scoped_device(queries, gallery, norms, groups, k: int, only=N
     return _topk_scoped(queries, gallery, norms, groups, k, only, exclude, keep, want_sim)
 
 
+RETRIEVAL_RANGE_BLOCK = 128  # include/coot_hip.h: COOT_RETRIEVAL_RANGE_BLOCK
+
+
+def _check_threshold(fn: str, threshold, m: int):
+    """The threshold of a range search, checked on the host before anything is launched (ValueError): a Python or numpy number (used
+    for every query), M numbers on the host (a sequence, a numpy array or a CPU tensor) or a cuda torch.float32 tensor [M].  Returns
+    the cuda tensor, or a float32 numpy array [M] that the caller uploads once: a host value is rounded to float32 here, once."""
+    import torch
+    if isinstance(threshold, torch.Tensor) and threshold.is_cuda:
+        if threshold.dtype is not torch.float32:
+            raise ValueError(f"{fn}: threshold on the device has to be torch.float32, not {threshold.dtype}")
+        if tuple(threshold.shape) != (m,):
+            raise ValueError(f"{fn}: threshold of shape {tuple(threshold.shape)}, {m} queries (one number, or one per query: [{m}])")
+        return threshold
+    try:
+        t = np.asarray(threshold.numpy() if isinstance(threshold, torch.Tensor) else threshold)
+    except Exception:
+        t = np.asarray(None)
+    if t.dtype.kind not in "fiu":
+        raise ValueError(f"{fn}: threshold has to be a number or hold one number per query, not dtype {t.dtype}")
+    if t.shape not in ((), (m,)):
+        raise ValueError(f"{fn}: threshold of shape {tuple(t.shape)}, {m} queries (one number, or one per query: [{m}])")
+    with np.errstate(over="ignore"):
+        return np.array(np.broadcast_to(t.astype(np.float32), (m,)))  # (a copy: contiguous and writable)
+
+
+def _check_range_result(fn: str, max_results, order):
+    """max_results (None or an integer >= 1) and order ("row" or "score", the latter with max_results=None only), or the ValueError."""
+    if order not in ("row", "score"):
+        raise ValueError(f"{fn}: order = {order!r}; it has to be \"row\" or \"score\"")
+    if max_results is not None and (isinstance(max_results, bool) or not isinstance(max_results, (int, np.integer)) or max_results < 1):
+        raise ValueError(f"{fn}: max_results = {max_results!r}; it has to be None (the exact size, one synchronisation) or an integer >= 1")
+    if order == "score" and max_results is not None:
+        raise ValueError(f"{fn}: order=\"score\" needs max_results=None: a segment that was cut has no defined score order")
+
+
+def _range(queries, gallery, norms, threshold, keep, max_results, order, method=None, own_keep=None, count_only: bool = False):
+    """coot_retrieval_range_count / _scan / _fill for any M: slices of RETRIEVAL_FEW_MAX queries over one workspace and one table of block
+    counts.  Checked in this order: max_results and order, keep, the threshold's type and shape, then where everything lives.  method,
+    own_keep: the name and the own filter of GalleryIndex.search_range / count_range; count_only: the counts after the scan, no fill."""
+    import torch
+    from . import lib as _lib
+    fn = "retrieval_range_device"
+    who = method or fn
+    if not count_only:
+        _check_range_result(who, max_results, order)
+    assert gallery.dim() == 2, gallery.shape
+    if keep is not None:
+        keep = _check_keep(who, keep, gallery.shape[0], mirror=None)
+    queries = queries[None] if queries.dim() == 1 else queries
+    assert queries.dim() == 2, queries.shape
+    thr = _check_threshold(who, threshold, queries.shape[0])
+    (queries, gallery, norms), code, (m, n, d, _) = _check_search(fn, "compute_retrieval_range", queries, gallery, norms, 1, queries.dtype,
+                                                                  also=(keep,), method=method)
+    dev = queries.device
+    if isinstance(thr, np.ndarray):
+        thr = torch.from_numpy(thr).to(dev)
+    elif thr.device != dev:
+        raise ValueError(f"{who}: threshold lives on {thr.device}, the queries on {dev}")
+    thr = thr.contiguous()
+    keep = _and_own(own_keep, keep)
+    lib = _lib.load()
+    stride = (n + RETRIEVAL_RANGE_BLOCK - 1) // RETRIEVAL_RANGE_BLOCK + 1
+    table = torch.empty(m, stride, dtype=torch.int32, device=dev)
+    ws = torch.empty(lib.coot_retrieval_range_workspace_bytes(min(m, RETRIEVAL_FEW_MAX), n, d), dtype=torch.uint8, device=dev)
+    st = _stream()
+    slices = [(i, min(RETRIEVAL_FEW_MAX, m - i)) for i in range(0, m, RETRIEVAL_FEW_MAX)]  # the calls of a stream run in order: one workspace
+    for i, mm in slices:
+        _lib.check(lib.coot_retrieval_range_count(queries[i:].data_ptr(), gallery.data_ptr(), code, _ptr(norms), _ptr(keep), thr[i:].data_ptr(), mm, n, d,
+                                                  table[i:].data_ptr(), ws.data_ptr(), ws.numel(), st), "coot_retrieval_range_count")
+    counts = torch.empty(m, dtype=torch.int32, device=dev)
+    offsets = None if count_only else torch.empty(m + 1, dtype=torch.int64, device=dev)
+    _lib.check(lib.coot_retrieval_range_scan(table.data_ptr(), m, n, _ptr(offsets), counts.data_ptr(), st), "coot_retrieval_range_scan")
+    if count_only:
+        return counts
+    if max_results is None:
+        cap = int(offsets[m])  # (the one synchronisation)
+        rows = torch.empty(cap, dtype=torch.int32, device=dev)
+        scores = torch.empty(cap, dtype=torch.float32, device=dev)
+        if cap == 0:
+            return offsets, rows, scores
+    else:
+        cap = int(max_results)
+        rows = torch.full((cap,), -1, dtype=torch.int32, device=dev)
+        scores = torch.full((cap,), float("-inf"), dtype=torch.float32, device=dev)
+    for i, mm in slices:
+        _lib.check(lib.coot_retrieval_range_fill(queries[i:].data_ptr(), gallery.data_ptr(), code, _ptr(norms), _ptr(keep), thr[i:].data_ptr(), mm, n, d,
+                                                 table[i:].data_ptr(), offsets[i:].data_ptr(), cap, rows.data_ptr(), scores.data_ptr(), ws.data_ptr(),
+                                                 ws.numel(), st), "coot_retrieval_range_fill")
+    if order == "score":
+        # the searches' order inside every segment: score descending with -0 as +0, then the larger row.  Stable sorts: reversed, the
+        # rows of a segment descend; then by score; then by segment, which keeps both.
+        seg = torch.repeat_interleave(torch.arange(m, device=dev), counts.long(), output_size=cap)
+        perm = torch.arange(cap - 1, -1, -1, device=dev)
+        perm = perm[torch.sort(scores[perm] + 0.0, descending=True, stable=True)[1]]
+        perm = perm[torch.sort(seg[perm], stable=True)[1]]
+        rows, scores = rows[perm], scores[perm]
+    return offsets, rows, scores
+
+
+def retrieval_range_device(queries, gallery, norms, threshold, keep=None, max_results=None, order: str = "row"):
+    """The range search on a gallery as a prepared index holds it (coot_retrieval_range_count, _scan, _fill): every gallery row that
+    scores at least a query's threshold, however many there are.  queries cuda float32 [M, d], gallery cuda float32, bfloat16 or
+    float16 [N, d], norms cuda float32 [N] (GalleryIndex.norms) or None: rows used as they are.  threshold: a Python number (for every
+    query), M numbers on the host (a sequence, a numpy array or a CPU tensor; uploaded once) or a cuda torch.float32 tensor [M]; a host
+    value is rounded to float32 once.  Row j is a hit of query i when keep lets it pass and s(i, j) >= threshold[i] in float32, s being
+    the similarity the searches rank on, bit for bit (sim of GalleryIndex.search(..., want_sim=True)): a NaN score or threshold is no
+    hit, -0 >= +0 holds, -inf returns every kept row whose score is not a NaN, +inf only rows that score +inf.
+    Returns (offsets int64 [M + 1], rows int32 [T], scores float32 [T]) on the device, CSR: the hits of query i are
+    rows[offsets[i]:offsets[i + 1]], in ascending row order, with their scores — compute_retrieval_range of the similarities, byte for
+    byte, whatever the batch-mates of a query, the storage type and the schedule are; no M x N matrix and no top-K cap of 128.
+    max_results=None: T = offsets[M] is read back, the one synchronisation, and rows / scores have exactly T entries.  max_results=c >=
+    1: nothing synchronises; rows / scores have c entries, the first min(T, c) of the result and then -1 / -inf; offsets is exact
+    either way, so offsets[M] > c says that, and where, the result was cut.  order="score" (max_results=None only: ValueError
+    otherwise) puts every segment into the searches' order, score descending with -0 as +0, then the larger row, with torch sorts on
+    the device.  More than 16 queries run in slices of 16 over one workspace: per slice one sweep of the gallery that counts, and one
+    that reads only the blocks of 128 rows in which a query of the slice has a hit."""
+    return _range(queries, gallery, norms, threshold, keep, max_results, order)
+
+
 # retrieval_topk_multi_device: the table best [M][G] of one library call holds at most this many entries (2^25 x 8 bytes = 256 MiB); a
 # larger search runs as several calls, split where a paragraph ends, over one workspace.  One paragraph is never split: its own table
 # may reach the library's bound.
@@ -511,6 +634,9 @@ class GalleryIndex:
     checked and its rows outside [0, N) are ignored.  restore() clears the filter.  search combines index.keep with its own keep by
     logical AND.  Removed rows still occupy memory until compact(): the gallery bytes and the norms are untouched, only the selection
     skips them.
+
+    Range search.  search_range(queries, threshold) returns every row at or above a query's threshold, however many, as CSR (offsets,
+    rows, scores), and count_range their number: see the methods.  keep and the index's own filter apply as in search.
 
     Growth.  index.n (= len(index)) rows are searched, index.capacity rows fit the buffer; index.gallery, index.norms and index.keep
     are the first n rows of it, reassigned whenever n changes (a reference taken earlier keeps the rows it had).  capacity=None is the
@@ -781,6 +907,26 @@ class GalleryIndex:
         index does not store groups; the caller owns the table across add() and compact(), as in search_grouped."""
         return _topk_scoped(queries, self.gallery, self.norms if self.normalize else None, groups, k, only, exclude, keep, want_sim,
                             method="GalleryIndex.search_scoped", own_keep=self.keep)
+
+    def search_range(self, queries, threshold, keep=None, max_results=None, order: str = "row"):
+        """EVERY row that scores at least the query's threshold, however many there are: (offsets int64 [M + 1], rows int32 [T], scores
+        float32 [T]) on the device, CSR — the hits of query i are rows[offsets[i]:offsets[i + 1]], in ascending row order, with their
+        scores.  threshold: a Python number, M numbers on the host or a cuda torch.float32 tensor [M].  A hit is a row that keep and
+        the index's own filter (remove) let pass with s(i, j) >= threshold[i] in float32, s being the similarity search() ranks on,
+        bit for bit: compute_retrieval_range of the sim that search(queries, k, want_sim=True) returns, byte for byte, for every
+        storage type and whatever else is in the batch.  What search(queries, 128) filtered by a threshold cannot give once more than
+        128 rows qualify, and without the M x N matrix of queries @ gallery.T >= t.  max_results=None reads the size back (the one
+        synchronisation) and allocates exactly; max_results=c never synchronises, returns c entries (-1 / -inf behind the result) and
+        leaves offsets exact, so offsets[M] > c tells that the result was cut.  order="score": every segment best first, as search()
+        orders (max_results=None only).  See retrieval_range_device."""
+        return _range(queries, self.gallery, self.norms if self.normalize else None, threshold, keep, max_results, order,
+                      method="GalleryIndex.search_range", own_keep=self.keep)
+
+    def count_range(self, queries, threshold, keep=None):
+        """How many rows search_range would return per query, int32 [M] on the device: the counting sweep and the scan, no
+        synchronisation and no second sweep.  (The distractors that beat a ground truth: threshold = its score.)"""
+        return _range(queries, self.gallery, self.norms if self.normalize else None, threshold, keep, None, "row",
+                      method="GalleryIndex.count_range", own_keep=self.keep, count_only=True)
 
     def neighbors(self, rows, k: int, groups=None, keep=None):
         """More like this: the k best rows for each of the index's own rows, (idx int32 [R, k], scores float32 [R, k]) on the device.

@@ -7,6 +7,7 @@ compute_retrieval_topk (_masked, _grouped, _multi, _scoped): WHICH gallery items
 on a similarity matrix [M, N], M and N independent; under a keep flag per gallery row; the K best GROUPS of rows, each through its
 best row; the K best groups for a PARAGRAPH of queries (MaxSim), whose offsets _host_offsets checks for mirror and device wrappers
 alike; under a mask per QUERY, the rows with (only) or without (exclude) the id the query brings.
+compute_retrieval_range: every column at or above a row's threshold, however many, as CSR.
 compute_retrieval_labeled: ranks and metrics without the assumption "square, ground truth on the diagonal": labels[i] = the gallery
 row of query i; several queries per row, rows without a query and queries without a row (a label outside [0, N)) are allowed.
 strip_bounds / compute_retrieval_counts_part: one strip of rows of the sharded validation; the sum over the strips is the whole."""
@@ -122,6 +123,39 @@ def compute_retrieval_topk_scoped(sim: np.ndarray, k: int, groups, only=None, ex
     for i in range(m):
         idx[i], scores[i] = compute_retrieval_topk_masked(sim[i:i + 1], k, ok & ((groups == scope[i]) == (only is not None)))
     return idx, scores
+
+
+def compute_retrieval_range(sim: np.ndarray, threshold, keep=None, order: str = "row") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Every column of sim [M, N] that scores at least the row's threshold: (offsets int64 [M + 1], rows int32 [T], scores [T]), CSR:
+    the hits of row i are rows[offsets[i]:offsets[i + 1]] with scores = sim[i, rows], T = offsets[M].  threshold: one number or [M]
+    numbers, rounded to float32 once.  Column j is a hit of row i when keep[j] != 0 (keep [N] booleans or bytes, None: every column)
+    and sim[i, j] >= threshold[i], the IEEE compare: a NaN on either side is no hit, -0 >= +0 holds, -inf takes every kept column that
+    is not a NaN, +inf only columns that are +inf.  order="row": a segment's columns ascend.  order="score": the order of
+    compute_retrieval_topk_masked inside every segment, score descending (-0 as +0), then column descending."""
+    sim = np.asarray(sim)
+    assert sim.ndim == 2 and order in ("row", "score"), (sim.shape, order)
+    m, n = sim.shape
+    with np.errstate(over="ignore"):
+        t = np.asarray(threshold).astype(np.float32)
+    assert t.shape in ((), (m,)), (t.shape, m)
+    t = np.broadcast_to(t, (m,))
+    ok = np.ones(n, bool)
+    if keep is not None:
+        keep = np.asarray(keep)
+        assert keep.shape == (n,), (keep.shape, n)
+        ok = keep != 0
+    offsets = np.zeros(m + 1, np.int64)
+    segs = []
+    for i in range(m):
+        with np.errstate(invalid="ignore"):
+            cols = np.nonzero(ok & (sim[i] >= t[i]))[0]
+        if order == "score":  # ascending and stable, reversed: score, then column, descending (no NaN is a hit)
+            cols = cols[np.argsort(sim[i, cols], kind="stable")[::-1]]
+        segs.append(cols)
+        offsets[i + 1] = offsets[i] + len(cols)
+    rows = np.concatenate(segs).astype(np.int32) if segs else np.zeros(0, np.int32)
+    scores = np.concatenate([sim[i, c] for i, c in enumerate(segs)]) if segs else np.zeros(0, sim.dtype)
+    return offsets, rows, scores.astype(sim.dtype)
 
 
 def _host_offsets(fn: str, offsets, m: int, exc=ValueError) -> np.ndarray:

@@ -524,6 +524,45 @@ int coot_retrieval_topk_scoped(const float* queries, const void* gallery, int ga
                                const int32_t* groups, const int32_t* scope, int exclude, int M, int N, int d, int K, int32_t* idx_out,
                                float* score_out, float* sim_out, void* workspace, size_t workspace_bytes, coot_stream_t stream);
 
+/* ---- range search: every gallery row at or above a query's threshold ------------------------------------------------------------
+ * Row j is a hit of query i when it passes keep (NULL: no filter) and s(i, j) >= thresholds[i], an IEEE fp32 compare: a NaN score or a
+ * NaN threshold is no hit, -0 >= +0 holds, -inf returns every kept row whose score is not a NaN, +inf only rows that score +inf.
+ * s(i, j) is the fp32 similarity every search here ranks on, bit for bit the sim_out of coot_retrieval_topk_few_masked.  The result is
+ * CSR: offsets int64 [M + 1], offsets[0] = 0, and the hits of query i at offsets[i] .. offsets[i + 1] - 1 of rows_out (int32) and
+ * scores_out (fp32, the bytes of s), in ascending row order.  A hit's position is computed, never claimed through an atomic: the bytes
+ * do not depend on the schedule, on the other queries of a call or on the sweep's row splits (coot_set_option("rt_few_splits", n)).
+ * Three calls on one stream, because only the middle one sees all queries and only the caller knows how much room the result may take:
+ *   coot_retrieval_range_count: 1 <= M <= COOT_RETRIEVAL_FEW_MAX queries, one sweep of the gallery.  block_counts: the M rows of these
+ *     queries in a table of int32, COOT_RETRIEVAL_RANGE_TABLE_ROW(N) entries per query (one per block of COOT_RETRIEVAL_RANGE_BLOCK
+ *     gallery rows, and one more); it writes the first ceil(N / 128) entries of each row, the query's hits per block.  A block in
+ *     which keep leaves no row is not read.  A search of more queries calls it once per 16, each on its rows of one table.
+ *   coot_retrieval_range_scan: any M >= 1, all rows of the table at once: every row becomes the exclusive prefix of its counts with
+ *     the query's total in its last entry; counts_out (int32 [M], optional) takes the totals, offsets (int64 [M + 1], optional) their
+ *     prefix.  With offsets == NULL it is a count of hits and nothing more.  Nothing is read back: the host learns sizes only if the
+ *     caller copies offsets[M].
+ *   coot_retrieval_range_fill: the count call's arguments again (the same M queries, thresholds and keep), block_base = those queries'
+ *     rows of the scanned table, offsets = their M entries of the offsets (offsets + i0 for queries i0 ..), and rows_out / scores_out
+ *     with room for `capacity` entries: a hit whose position is below capacity is written, the others are not, and entries that no
+ *     hit claims are not touched (a caller that cuts the result presets them).  It sweeps again, the same chain and so the same bits,
+ *     but a block in which none of the call's queries has a hit is not read: under a selective threshold it reads few blocks.
+ *   gallery_dtype COOT_GALLERY_F32, _BF16 or _F16; gallery_norms NULL: rows used as they are; thresholds: device fp32 [M].
+ * workspace (16-byte aligned) of count and fill: coot_retrieval_range_workspace_bytes(M, N, d); it needs no device and is 256 for
+ * arguments out of range.  count reads queries, gallery, gallery_norms, keep, thresholds and writes block_counts and the workspace;
+ * scan reads and writes block_counts and writes offsets and counts_out; fill reads what count reads, block_base and offsets, and writes
+ * rows_out, scores_out and the workspace.  A refused call (unknown dtype, a null pointer other than gallery_norms, keep, offsets and
+ * counts_out of the scan, M outside its range, N or d < 1, capacity < 0, workspace misaligned or too small) returns before any launch and
+ * writes nothing.  No allocation, no synchronisation; no pointer is retained. */
+#define COOT_RETRIEVAL_RANGE_BLOCK 128
+#define COOT_RETRIEVAL_RANGE_TABLE_ROW(N) (((N) + COOT_RETRIEVAL_RANGE_BLOCK - 1) / COOT_RETRIEVAL_RANGE_BLOCK + 1)
+size_t coot_retrieval_range_workspace_bytes(int M, int N, int d);
+int coot_retrieval_range_count(const float* queries, const void* gallery, int gallery_dtype, const float* gallery_norms, const uint8_t* keep,
+                               const float* thresholds, int M, int N, int d, int32_t* block_counts, void* workspace, size_t workspace_bytes,
+                               coot_stream_t stream);
+int coot_retrieval_range_scan(int32_t* block_counts, int M, int N, int64_t* offsets, int32_t* counts_out, coot_stream_t stream);
+int coot_retrieval_range_fill(const float* queries, const void* gallery, int gallery_dtype, const float* gallery_norms, const uint8_t* keep,
+                              const float* thresholds, int M, int N, int d, const int32_t* block_base, const int64_t* offsets, int64_t capacity,
+                              int32_t* rows_out, float* scores_out, void* workspace, size_t workspace_bytes, coot_stream_t stream);
+
 /* ---- a prepared gallery that changes: rows written in place, their norms with them ---------------------------------------
  * coot_retrieval_rows_put writes the R rows of src [R, d] into the buffer gallery [N, d] and, where norms != NULL, norms[row] of
  * every row it wrote: what a corpus that grows (rows appended into spare capacity) or is re-encoded (rows overwritten) needs,
