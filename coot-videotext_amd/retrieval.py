@@ -17,7 +17,8 @@ groups for a PARAGRAPH of queries (compute_retrieval_topk_multi): coot_retrieval
 GalleryIndex.search_scoped: every query inside (only=) or outside (exclude=) the rows with the id it brings
 (compute_retrieval_topk_scoped): coot_retrieval_topk_scoped; GalleryIndex.neighbors: a row's neighbours outside its own group.
 retrieval_range_device / GalleryIndex.search_range, count_range: every row at or above a query's threshold, however many, as CSR
-(compute_retrieval_range): coot_retrieval_range_count, _scan, _fill (_range).
+(compute_retrieval_range): coot_retrieval_range_count, _scan, _fill for up to RANGE_TILE_MIN_M* - 1 queries, in slices of 16, and
+coot_retrieval_range_tile_count, _scan, _tile_fill from there on, one call per pass (_range).
 The searches on a prepared gallery share one host check (_check_search) and have one implementation per library call (_topk_few,
 _topk_tile, _topk_grouped, _topk_multi, _topk_scoped), which the public wrapper and the GalleryIndex method both call.
 GalleryIndex.add / update / compact: rows appended or overwritten in place together with their norms (coot_retrieval_rows_put),
@@ -377,6 +378,18 @@ def retrieval_topk_scoped_device(queries, gallery, norms, groups, k: int, only=N
 
 RETRIEVAL_RANGE_BLOCK = 128  # include/coot_hip.h: COOT_RETRIEVAL_RANGE_BLOCK
 
+# The range search: from this many queries on, one tile call per pass over all queries (coot_retrieval_range_tile_count / _fill, 64
+# queries per workgroup and read of a gallery block); below it, slices of RETRIEVAL_FEW_MAX queries through the sweep, two sweeps of the
+# gallery each.  RANGE_TILE_MIN_M: a float32 gallery; RANGE_TILE_MIN_M_16BIT: bfloat16 / float16.  Both routes return the same bytes;
+# up to RETRIEVAL_FEW_MAX queries the sweep always serves.  Read at call time.
+# Each is the smallest M of the measured ladder (profiles/r25_range_tile.json: M = 17, 32, 64, 128, 256, 512, 1 024; 200 000 x 768 and
+# 18 000 x 384; 2 rows, 0.1 % and 10 % of the gallery per query) from which the tile route's median stays below the slices' median by
+# more than the slices' own spread in every case.  At 17 queries the one row tile is a quarter full: at 200 000 x 768 the tile route
+# then loses on bfloat16 (0.96 against 0.84 ms at 0.1 %) and is inside the spread on float32 (0.95 against 0.99 +- 0.15 ms); at
+# 18 000 x 384 it already wins at 17 (0.15 against 0.22 ms), which this one threshold leaves to the slices.
+RANGE_TILE_MIN_M = 32
+RANGE_TILE_MIN_M_16BIT = 32
+
 
 def _check_threshold(fn: str, threshold, m: int):
     """The threshold of a range search, checked on the host before anything is launched (ValueError): a Python or numpy number (used
@@ -413,7 +426,8 @@ def _check_range_result(fn: str, max_results, order):
 
 def _range(queries, gallery, norms, threshold, keep, max_results, order, method=None, own_keep=None, count_only: bool = False):
     """coot_retrieval_range_count / _scan / _fill for any M: slices of RETRIEVAL_FEW_MAX queries over one workspace and one table of block
-    counts.  Checked in this order: max_results and order, keep, the threshold's type and shape, then where everything lives.  method,
+    counts; from RANGE_TILE_MIN_M (float32 gallery) / RANGE_TILE_MIN_M_16BIT queries on, coot_retrieval_range_tile_count and _tile_fill
+    instead, one call each over all queries on the same table, with the same scan between them.  Checked in this order: max_results and order, keep, the threshold's type and shape, then where everything lives.  method,
     own_keep: the name and the own filter of GalleryIndex.search_range / count_range; count_only: the counts after the scan, no fill."""
     import torch
     from . import lib as _lib
@@ -439,9 +453,16 @@ def _range(queries, gallery, norms, threshold, keep, max_results, order, method=
     lib = _lib.load()
     stride = (n + RETRIEVAL_RANGE_BLOCK - 1) // RETRIEVAL_RANGE_BLOCK + 1
     table = torch.empty(m, stride, dtype=torch.int32, device=dev)
-    ws = torch.empty(lib.coot_retrieval_range_workspace_bytes(min(m, RETRIEVAL_FEW_MAX), n, d), dtype=torch.uint8, device=dev)
+    tile = m >= (RANGE_TILE_MIN_M_16BIT if code else RANGE_TILE_MIN_M)
     st = _stream()
-    slices = [(i, min(RETRIEVAL_FEW_MAX, m - i)) for i in range(0, m, RETRIEVAL_FEW_MAX)]  # the calls of a stream run in order: one workspace
+    if tile:  # one call per pass, all queries
+        ws = torch.empty(lib.coot_retrieval_range_tile_workspace_bytes(m, n, d), dtype=torch.uint8, device=dev)
+        slices = []
+        _lib.check(lib.coot_retrieval_range_tile_count(queries.data_ptr(), gallery.data_ptr(), code, _ptr(norms), _ptr(keep), thr.data_ptr(), m, n, d,
+                                                       table.data_ptr(), ws.data_ptr(), ws.numel(), st), "coot_retrieval_range_tile_count")
+    else:
+        ws = torch.empty(lib.coot_retrieval_range_workspace_bytes(min(m, RETRIEVAL_FEW_MAX), n, d), dtype=torch.uint8, device=dev)
+        slices = [(i, min(RETRIEVAL_FEW_MAX, m - i)) for i in range(0, m, RETRIEVAL_FEW_MAX)]  # the calls of a stream run in order: one workspace
     for i, mm in slices:
         _lib.check(lib.coot_retrieval_range_count(queries[i:].data_ptr(), gallery.data_ptr(), code, _ptr(norms), _ptr(keep), thr[i:].data_ptr(), mm, n, d,
                                                   table[i:].data_ptr(), ws.data_ptr(), ws.numel(), st), "coot_retrieval_range_count")
@@ -460,6 +481,10 @@ def _range(queries, gallery, norms, threshold, keep, max_results, order, method=
         cap = int(max_results)
         rows = torch.full((cap,), -1, dtype=torch.int32, device=dev)
         scores = torch.full((cap,), float("-inf"), dtype=torch.float32, device=dev)
+    if tile:
+        _lib.check(lib.coot_retrieval_range_tile_fill(queries.data_ptr(), gallery.data_ptr(), code, _ptr(norms), _ptr(keep), thr.data_ptr(), m, n, d,
+                                                      table.data_ptr(), offsets.data_ptr(), cap, rows.data_ptr(), scores.data_ptr(), ws.data_ptr(),
+                                                      ws.numel(), st), "coot_retrieval_range_tile_fill")
     for i, mm in slices:
         _lib.check(lib.coot_retrieval_range_fill(queries[i:].data_ptr(), gallery.data_ptr(), code, _ptr(norms), _ptr(keep), thr[i:].data_ptr(), mm, n, d,
                                                  table[i:].data_ptr(), offsets[i:].data_ptr(), cap, rows.data_ptr(), scores.data_ptr(), ws.data_ptr(),
@@ -491,7 +516,9 @@ def retrieval_range_device(queries, gallery, norms, threshold, keep=None, max_re
     either way, so offsets[M] > c says that, and where, the result was cut.  order="score" (max_results=None only: ValueError
     otherwise) puts every segment into the searches' order, score descending with -0 as +0, then the larger row, with torch sorts on
     the device.  More than 16 queries run in slices of 16 over one workspace: per slice one sweep of the gallery that counts, and one
-    that reads only the blocks of 128 rows in which a query of the slice has a hit."""
+    that reads only the blocks of 128 rows in which a query of the slice has a hit.  From RANGE_TILE_MIN_M queries on a float32 gallery
+    and RANGE_TILE_MIN_M_16BIT on a 16-bit one (module constants, read at call time) the route changes to two tile calls over all
+    queries, 64 queries per read of a block; the bytes of the result do not."""
     return _range(queries, gallery, norms, threshold, keep, max_results, order)
 
 
@@ -918,13 +945,15 @@ class GalleryIndex:
         128 rows qualify, and without the M x N matrix of queries @ gallery.T >= t.  max_results=None reads the size back (the one
         synchronisation) and allocates exactly; max_results=c never synchronises, returns c entries (-1 / -inf behind the result) and
         leaves offsets exact, so offsets[M] > c tells that the result was cut.  order="score": every segment best first, as search()
-        orders (max_results=None only).  See retrieval_range_device."""
+        orders (max_results=None only).  Up to RANGE_TILE_MIN_M - 1 queries (RANGE_TILE_MIN_M_16BIT - 1 on a 16-bit index) run in
+        slices of 16 through the sweep, more in two tile calls over all queries; the bytes are the same.  See retrieval_range_device."""
         return _range(queries, self.gallery, self.norms if self.normalize else None, threshold, keep, max_results, order,
                       method="GalleryIndex.search_range", own_keep=self.keep)
 
     def count_range(self, queries, threshold, keep=None):
-        """How many rows search_range would return per query, int32 [M] on the device: the counting sweep and the scan, no
-        synchronisation and no second sweep.  (The distractors that beat a ground truth: threshold = its score.)"""
+        """How many rows search_range would return per query, int32 [M] on the device: the counting sweep (from RANGE_TILE_MIN_M /
+        RANGE_TILE_MIN_M_16BIT queries on: the counting tile call, as in search_range) and the scan, no synchronisation and no second
+        sweep.  (The distractors that beat a ground truth: threshold = its score.)"""
         return _range(queries, self.gallery, self.norms if self.normalize else None, threshold, keep, None, "row",
                       method="GalleryIndex.count_range", own_keep=self.keep, count_only=True)
 

@@ -563,6 +563,34 @@ int coot_retrieval_range_fill(const float* queries, const void* gallery, int gal
                               const float* thresholds, int M, int N, int d, const int32_t* block_base, const int64_t* offsets, int64_t capacity,
                               int32_t* rows_out, float* scores_out, void* workspace, size_t workspace_bytes, coot_stream_t stream);
 
+/* ---- range search for many queries: the count and the fill pass on the 64 x 64 tile -----------------------------------------------
+ * The range search above, same hit rule, same table, same scan, same CSR result, for any number of queries in one call per pass:
+ *   coot_retrieval_range_tile_count: any M >= 1 with ceil(M / 64) <= 65535.  block_counts: the whole table, int32
+ *     [M][COOT_RETRIEVAL_RANGE_TABLE_ROW(N)]; it writes the first ceil(N / 128) entries of every row, slot for slot what
+ *     coot_retrieval_range_count writes for the same queries in calls of 16.  A workgroup serves 64 queries and a block of 128 rows; a
+ *     block in which keep leaves no row is not read.
+ *   coot_retrieval_range_scan, unchanged, on the table.
+ *   coot_retrieval_range_tile_fill: the count call's arguments again, block_base = the scanned table, offsets = the scan's offsets (all
+ *     M + 1; M are read), and rows_out / scores_out with room for `capacity` entries: a hit whose position is below capacity is written,
+ *     the others are not, and entries that no hit claims are not touched.  A block in which none of a workgroup's 64 queries has a hit
+ *     is not read by that workgroup.
+ * s(i, j) is the same fp32 chain as in every other search, so table, offsets, rows and scores are byte for byte those of the three
+ * calls above, whichever pass ran on which route; they do not depend on the schedule or on the other queries of the call.  No atomic
+ * touches global memory.  gallery_dtype, gallery_norms (NULL: rows used as they are; otherwise the queries' norms are computed into the
+ * workspace), keep (NULL: no filter) and thresholds (device fp32 [M]) as above.
+ * workspace (16-byte aligned): coot_retrieval_range_tile_workspace_bytes(M, N, d), the query norms; it needs no device and is 256 for
+ * arguments out of range.  count reads queries, gallery, gallery_norms, keep, thresholds and writes block_counts and the workspace; fill
+ * reads what count reads, block_base and offsets, and writes rows_out, scores_out and the workspace.  A refused call (unknown dtype, a
+ * null pointer other than gallery_norms and keep, M outside its range, N or d < 1, capacity < 0, workspace misaligned or too small)
+ * returns before any launch and writes nothing.  No allocation, no synchronisation; no pointer is retained. */
+size_t coot_retrieval_range_tile_workspace_bytes(int M, int N, int d);
+int coot_retrieval_range_tile_count(const float* queries, const void* gallery, int gallery_dtype, const float* gallery_norms, const uint8_t* keep,
+                                    const float* thresholds, int M, int N, int d, int32_t* block_counts, void* workspace, size_t workspace_bytes,
+                                    coot_stream_t stream);
+int coot_retrieval_range_tile_fill(const float* queries, const void* gallery, int gallery_dtype, const float* gallery_norms, const uint8_t* keep,
+                                   const float* thresholds, int M, int N, int d, const int32_t* block_base, const int64_t* offsets, int64_t capacity,
+                                   int32_t* rows_out, float* scores_out, void* workspace, size_t workspace_bytes, coot_stream_t stream);
+
 /* ---- a prepared gallery that changes: rows written in place, their norms with them ---------------------------------------
  * coot_retrieval_rows_put writes the R rows of src [R, d] into the buffer gallery [N, d] and, where norms != NULL, norms[row] of
  * every row it wrote: what a corpus that grows (rows appended into spare capacity) or is re-encoded (rows overwritten) needs,
