@@ -665,6 +665,9 @@ extern "C" void coot_step_grad_write(int on);
 extern "C" void coot_step_det_seg_flush(int on);
 extern "C" int coot_step_det_seg_flush_get(void);
 extern "C" int coot_internal_stage_hits(void);
+extern "C" void coot_step_text_ahead(int on);
+extern "C" int coot_step_text_ahead_get(void);
+extern "C" int coot_internal_text_ahead_steps(void);
 extern "C" int coot_internal_stream_counter(int which);  // api_step.hip: StreamPicker
 extern "C++" { namespace coot { int det_bypass_count(); int det_overflow_count(); int det_set_overflow_guard(int on); int det_overflow_guard(); } }  // det.hip
 extern "C++" { namespace coot { void set_rt_topk_splits(int n); int get_rt_topk_splits(); void set_rt_few_splits(int n); int get_rt_few_splits(); void set_rt_grouped_splits(int n); int get_rt_grouped_splits(); } }  // retrieval_tile.hip, retrieval_few.hip, retrieval_grouped.hip
@@ -674,6 +677,8 @@ int coot_get_option(const char* name, int* value) {
   if (!strcmp(name, "xcd_order")) { *value = get_xcd_order(); return 0; }
   if (!strcmp(name, "tn_mode")) { *value = get_tn_mode(); return 0; }
   if (!strcmp(name, "stage_hits")) { *value = coot_internal_stage_hits(); return 0; }  // steps of this thread that used a prepared input stage
+  if (!strcmp(name, "text_ahead")) { *value = coot_step_text_ahead_get(); return 0; }
+  if (!strcmp(name, "text_ahead_steps")) { *value = coot_internal_text_ahead_steps(); return 0; }  // steps of this thread whose text side started ahead of main_s (COOT_STEP_TEXT_AHEAD)
   if (!strcmp(name, "fused_attn_launches")) { *value = fused_attn_launches(); return 0; }
   // concurrent-stream selection of this thread (coot_stream_create_concurrent, the library's own stream): spin-kernel tests run,
   // candidates that shared a hardware queue with a stream they have to run beside, selections that found no concurrent stream at all
@@ -708,6 +713,7 @@ int coot_set_option(const char* name, int value) {
   if (!strcmp(name, "xcd_order")) { set_xcd_order(value); return 0; }
   if (!strcmp(name, "grad_write")) { coot_step_grad_write(value); return 0; }
   if (!strcmp(name, "det_seg_flush")) { coot_step_det_seg_flush(value); return 0; }
+  if (!strcmp(name, "text_ahead")) { coot_step_text_ahead(value); return 0; }  // 0: COOT_STEP_TEXT_AHEAD is ignored, the text side forks from main_s as every step did
   if (!strcmp(name, "det_overflow_check")) return det_set_overflow_guard(value);  // 1: wrapped fixed-point adds poison their word with NaN (det.h; synchronises)  // 0: deterministic steps flush whole arenas in launches of their own
   if (!strcmp(name, "glob_flush_aux")) { g_glob_flush_aux = value; return 0; }
   if (!strcmp(name, "pool_handover")) { g_pool_handover_on = value; return 0; }  // 0: the pack between the local and the global forward stays a launch of its own  // 0: the global network's weight-gradient launch stays on its side's stream

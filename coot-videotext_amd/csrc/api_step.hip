@@ -340,6 +340,11 @@ struct InputPipe {
   }
 };
 thread_local InputPipe g_pipe;
+// Text side ahead (COOT_STEP_TEXT_AHEAD; coot_set_option("text_ahead", 0/1), default 1): a back-to-back step starts its text side
+// behind side_t's own tail instead of behind main_s — coot_train_step, at the fork
+int g_text_ahead = 1;
+thread_local hipStream_t g_text_deferred_on = nullptr;  // side_t of this thread's last coot_train_step if it deferred its text join, else null
+thread_local int g_text_ahead_steps = 0;                // steps of this thread that took the short fork (coot_get_option("text_ahead_steps"))
 struct StageScope { ~StageScope() { coot_internal_set_input_stage(nullptr, nullptr, 0); } };  // no exit path leaves a stage set
 // what a step (coot_train_step, or coot_step_forward ... coot_step_backward) knows about its stages
 struct PipeStep { bool piped = false, hit = false, prefetch = false; int cur = 0; StageLayout SL{}; };
@@ -347,11 +352,14 @@ thread_local PipeStep g_phase_pipe;  // of the phase calls: set by coot_step_for
 // this batch's x^ in stage[cur] (already there if the previous step normalised it: `hit`), the next batch's into the other
 // `announced`: the caller vouches that (x, d) is the batch it passed to coot_step_set_next_batch, unchanged (COOT_STEP_STAGE_ANNOUNCED).
 // Pointer and shape equality alone is not an identity: a loader's fixed-shape arena slot is refilled in place.
+bool pipe_hit(const coot_step_batch& x, const coot_step_dims& d, bool announced) {
+  return announced && g_pipe.ready && !memcmp(&g_pipe.have_x, &x, sizeof(x)) && !memcmp(&g_pipe.have_d, &d, sizeof(d));
+}
 int pipe_begin(const coot_step_config& cfg, const coot_step_batch& x, const coot_step_dims& d, hipStream_t sv, hipStream_t st, PipeStep& ps,
                bool announced) {
   ps = PipeStep{}; ps.piped = true;
   COOT_REQUIRE(g_pipe.stage[0] && g_pipe.stage[1], "step: input stages requested without coot_step_set_input_stages");
-  ps.hit = announced && g_pipe.ready && !memcmp(&g_pipe.have_x, &x, sizeof(x)) && !memcmp(&g_pipe.have_d, &d, sizeof(d));
+  ps.hit = pipe_hit(x, d, announced);
   ps.cur = ps.hit ? g_pipe.idx : (g_pipe.ready ? g_pipe.idx ^ 1 : 0);
   ps.SL = stage_layout(cfg, d, g_pipe.stage[ps.cur]);
   COOT_REQUIRE(ps.SL.bytes <= g_pipe.bytes, "step: input stages too small (%zu < %zu)", g_pipe.bytes, ps.SL.bytes);
@@ -1096,13 +1104,15 @@ int coot_sample_cycle_indices(const int64_t* clip_num, const int64_t* sent_num, 
 int coot_train_step(const coot_step_config* cfg, const coot_step_buffers* b, const coot_step_batch* x, const coot_step_dims* d,
                     float* losses, void* workspace, size_t workspace_bytes, int train, uint64_t seed, int64_t step, int do_optimizer,
                     coot_stream_t main_s, coot_stream_t side_v, coot_stream_t side_t) {
+  const hipStream_t deferred_on = g_text_deferred_on;  // (set again on the way out: an error return leaves it cleared)
+  g_text_deferred_on = nullptr;
   RUN(check_cfg(*cfg));
   COOT_REQUIRE(!COOT_OPERAND_IS_F16 || g_scaler, "coot_train_step: the f16 operand build is forward-only without a loss scaler (GradScaler: "
                "coot/trainer_retrieval.py:277-285; coot_step_set_loss_scaler); coot_step_forward runs");
   ScaledBwdScope scaled_bwd(g_scaler != nullptr);
   COOT_REQUIRE(losses, "train_step: losses pointer");
   COOT_REQUIRE((do_optimizer & ~(COOT_STEP_OPTIMIZER | COOT_STEP_REPACK | COOT_STEP_PACKS_FRESH | COOT_STEP_DEFER_TEXT_JOIN | COOT_STEP_INPUT_STAGES |
-                                 COOT_STEP_STAGE_ANNOUNCED)) == 0, "train_step: unknown bits in do_optimizer (%d)", do_optimizer);
+                                 COOT_STEP_STAGE_ANNOUNCED | COOT_STEP_TEXT_AHEAD)) == 0, "train_step: unknown bits in do_optimizer (%d)", do_optimizer);
   Bump A(workspace, workspace_bytes); StepWs W; layout_step(*cfg, *d, A, W);
   const SidePacked pk = side_packed(*x, *d);
   COOT_REQUIRE(!A.overflow, "train_step: workspace too small (%zu < %zu)", workspace_bytes, A.off);
@@ -1120,13 +1130,53 @@ int coot_train_step(const coot_step_config* cfg, const coot_step_buffers* b, con
                        cfg->eps, cfg->weight_decay, (unsigned long long)7919);
     COOT_CHECK_LAUNCH("step_state");
   }
-  RUN(g_hops.hop(0, sm, sv));
-  RUN(g_hops.hop(1, sm, st));
   const bool piped = (do_optimizer & COOT_STEP_INPUT_STAGES) != 0;
+  // ---- the fork.  The video side always starts behind main_s.  The text side does too (slot 1) — except back to back
+  // (COOT_STEP_TEXT_AHEAD): in the timed mode main_s IS the video stream, so "behind main_s" means behind the video side's update tail
+  // of the previous step (weight-gradient reduce -> input-FC parameter gradients -> Adam -> pack: four small dependent launches, ~55 us
+  // on an almost empty chip), and the text side, the later one at the forward's join, waited ~40 us for launches it takes nothing
+  // from (profiles/r07_kernel_timeline.txt).  With the flag the text side is ordered after side_t's own tail (stream order) and the
+  // stage event only.  What its forward touches before its first wait on the video stream (slot 6), and what orders each access:
+  //   reads   wpack[2], wpack[3], params[2], params[3] (biases)   written by the text side's update on side_t: stream order; those of
+  //           net 3 by the early update on the library's stream: slot 14, waited for at side_t's tail.  COOT_STEP_PACKS_FRESH is
+  //           required, so nobody else packed or touched them.
+  //   reads   x^ and the row positions in stage[cur]              written by the previous step's prefetch on the library's stream:
+  //           g_pipe.done (pipe_begin, kept).  The stage is a hit, so the raw features are not read at all.
+  //   reads   par_len, sent_len, sent_num, cu_txt, pe[2], pe[3]   the caller's; they were readable when the previous step's prefetch
+  //           read the batch (that step's video side started behind main_s and the prefetch behind it: slot 9 -> g_pipe.done), and the
+  //           caller vouches for everything it enqueued on main_s since (include/coot_hip.h)
+  //   writes  saved_lt, saved_gt, local_t, glob_t, resh_t, mask_t, lens_t  (layout_step: regions of the text side alone).  Last readers:
+  //           - the text side's own losses, backward and update on side_t: stream order;
+  //           - the (vid, par) contrastive launch on the video stream (glob_t, local_t): side_t waited for it in front of its backward
+  //             (slot 3);
+  //           - the weight-gradient launch of net 3 on the library's stream (glob_flush_aux: reads saved_gt and the text side's
+  //             scratch) and the early update behind it (slots 12 -> 14): slot 14 is recorded behind both, side_t waits for it at its tail;
+  //           - the previous step's prefetch passed saved_lt / local_t to coot_net_fwd in stage mode 1, which returns behind the
+  //             LayerNorm and touches neither; it is ordered by g_pipe.done anyway.
+  //           The video side's backward and update read none of them (its loss gradients d_local_v / d_resh_v are other regions).
+  //   records slots 10 and 2, launches nothing else before wait(6).
+  // One reader the short fork does NOT cover: without a next batch to prepare the zero fill runs on side_t behind its forward (below) and
+  // clears the video side's gradient arenas and the loss words, which the video side's update of the previous step reads and writes.
+  // That fill then waits for slot 1, recorded on main_s here (the hop's record, its wait moved from the fork to the fill).
+  // Not taken: with a loss scaler, a clip block or injected cycle indices (blocks and indices the caller prepares on main_s and side_t
+  // reads), under capture (a captured step forks from its origin), and whenever the step packs at its head.
+  bool ahead = (do_optimizer & COOT_STEP_TEXT_AHEAD) != 0 && g_text_ahead && piped && !pack_first && deferred_on == st && sm != st &&
+               !g_scaler && !g_clip && !g_cc_idx_inject && !g_state_dev && pipe_hit(*x, *d, (do_optimizer & COOT_STEP_STAGE_ANNOUNCED) != 0);
+  if (ahead) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(sm, &cs) != hipSuccess) { (void)hipGetLastError(); ahead = false; }
+    else ahead = cs == hipStreamCaptureStatusNone;
+  }
+  const bool fill_waits_main = ahead && !g_pipe.next_valid;
+  RUN(g_hops.hop(0, sm, sv));
+  if (!ahead) RUN(g_hops.hop(1, sm, st));
+  else if (fill_waits_main) RUN(g_hops.record(1, sm));
   StageScope stage_scope;
   PipeStep ps;
   COOT_REQUIRE(!(piped && g_state_dev), "train_step: input stages are not available in a replayable (captured) step");
   if (piped) RUN(pipe_begin(*cfg, *x, *d, sv, st, ps, (do_optimizer & COOT_STEP_STAGE_ANNOUNCED) != 0));
+  if (ahead) ++g_text_ahead_steps;
+  g_stamps.mark("text: forward starts", st);
   const StageLayout& SL = ps.SL; const bool hit = ps.hit;
   const bool prefetch = ps.prefetch;
   if (piped) coot_internal_set_input_stage(SL.xv, SL.pv, hit ? 2 : 0);
@@ -1159,6 +1209,7 @@ int coot_train_step(const coot_step_config* cfg, const coot_step_buffers* b, con
   // at the end of the text stream's forward)
   const hipStream_t sz = prefetch ? sv : st;
   if (prefetch) RUN(g_hops.wait(10, sv));
+  if (fill_waits_main) RUN(g_hops.wait(1, st));  // (text side ahead: the fill on side_t clears what the previous video update reads — the fork above)
   {
     const coot_net_config* cfgs[4] = {&cfg->net[0], &cfg->net[1], &cfg->net[2], &cfg->net[3]};
     float* extra[2] = {W.zero_begin, losses};
@@ -1267,12 +1318,16 @@ int coot_train_step(const coot_step_config* cfg, const coot_step_buffers* b, con
   g_stamps.mark("text: updated", st);
   RUN(g_hops.hop(4, sv, sm));
   if ((do_optimizer & COOT_STEP_DEFER_TEXT_JOIN) == 0) RUN(g_hops.hop(5, st, sm));  // else: the caller (or the next step's text side) orders it
+  else g_text_deferred_on = st;  // (what COOT_STEP_TEXT_AHEAD of the next step is checked against)
   g_stamps.mark("step done", sm);
   return 0;
 }
 
 void coot_step_stamps_enable(int on) { g_stamps.on = on != 0; }
 int coot_internal_stage_hits(void) { return g_pipe.hits; }
+void coot_step_text_ahead(int on) { g_text_ahead = on ? 1 : 0; }
+int coot_step_text_ahead_get(void) { return g_text_ahead; }
+int coot_internal_text_ahead_steps(void) { return g_text_ahead_steps; }
 size_t coot_step_device_state_bytes(void) { return sizeof(StepState); }
 int coot_step_set_device_state(void* state) {
   g_state_dev = (StepState*)state;
@@ -1381,6 +1436,7 @@ int coot_stream_destroy(coot_stream_t s) {
       g_streams.live.erase(g_streams.live.begin() + i);
       RUN(check_hip(hipStreamSynchronize((hipStream_t)s), "streamSynchronize"));
       if (g_pipe.checked && (g_pipe.beside[0] == (hipStream_t)s || g_pipe.beside[1] == (hipStream_t)s)) g_pipe.checked = false;  // (the handle may be reused)
+      if (g_text_deferred_on == (hipStream_t)s) g_text_deferred_on = nullptr;
       return check_hip(hipStreamDestroy((hipStream_t)s), "streamDestroy");
     }
   set_error("stream_destroy: not a stream of coot_stream_create_concurrent (of this thread)");

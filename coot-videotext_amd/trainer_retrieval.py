@@ -1183,6 +1183,10 @@ class RetrievalTrainer:
             flags |= _lib.STEP_INPUT_STAGES | (_lib.STEP_STAGE_ANNOUNCED if st.batch_announced else 0)
         if defer_join and do_optimizer:
             flags |= _lib.STEP_DEFER_TEXT_JOIN
+            # back to back (the previous call deferred its join and nobody joined since) on the announced batch: nothing enqueued on
+            # the current stream since then is for the text side — it may start behind its own stream's tail (COOT_STEP_TEXT_AHEAD)
+            if st.batch_announced and getattr(st, "join_pending", False):
+                flags |= _lib.STEP_TEXT_AHEAD
             st.join_pending = True
         else:
             st.join_pending = False  # this call ends with the text stream joined into the current one

@@ -698,7 +698,19 @@ size_t coot_step_workspace_bytes(const coot_step_config* cfg, const coot_step_di
                                    same streams needs no join (its text side continues on side_t in order, its video side touches
                                    nothing the text tail writes): back-to-back steps overlap that tail (~30 us) with the next
                                    forward.  Before anything else reads the text networks' parameters / packs from another
-                                   stream, the CALLER orders that stream after side_t.                                      */
+                                   stream, the CALLER orders that stream after side_t.  COOT_STEP_TEXT_AHEAD (below) lets that
+                                   next step start its text side without waiting for main_s at all.                        */
+#define COOT_STEP_TEXT_AHEAD 64 /* back-to-back steps: the caller vouches that nothing it enqueued on main_s since the previous
+                                   coot_train_step on these streams is needed by the text side, and that this previous step ended with
+                                   COOT_STEP_DEFER_TEXT_JOIN and has not been joined since.  The text side of this step is then ordered
+                                   after side_t's own tail and the input stage's event, NOT after main_s at entry: with side_v == main_s
+                                   its forward no longer waits for the video side's update tail of the previous step.  Taken only when
+                                   the step runs on a prepared input stage (COOT_STEP_INPUT_STAGES + COOT_STEP_STAGE_ANNOUNCED, a hit)
+                                   with COOT_STEP_PACKS_FRESH, side_t is the stream this thread's previous coot_train_step deferred
+                                   its join on, main_s is not being captured, and no loss scaler, gradient-clip block or injected cycle
+                                   indices are registered (the caller prepares those on main_s); in every other case the bit changes
+                                   nothing.  coot_set_option("text_ahead", 0) ignores it; coot_get_option("text_ahead_steps") counts
+                                   the steps of this thread that took it.  Same results either way.                        */
 int coot_train_step(const coot_step_config* cfg, const coot_step_buffers* bufs, const coot_step_batch* batch,
                     const coot_step_dims* dims, float* losses, void* workspace, size_t workspace_bytes, int train,
                     uint64_t seed, int64_t step, int do_optimizer, coot_stream_t main_stream, coot_stream_t side_v,
