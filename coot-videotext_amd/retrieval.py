@@ -19,6 +19,9 @@ GalleryIndex.search_scoped: every query inside (only=) or outside (exclude=) the
 retrieval_range_device / GalleryIndex.search_range, count_range: every row at or above a query's threshold, however many, as CSR
 (compute_retrieval_range): coot_retrieval_range_count, _scan, _fill for up to RANGE_TILE_MIN_M* - 1 queries, in slices of 16, and
 coot_retrieval_range_tile_count, _scan, _tile_fill from there on, one call per pass (_range).
+retrieval_self_join_device / GalleryIndex.self_join, count_self_join: the gallery against itself, all pairs (i, j), i < j, at or above
+row i's threshold, as the same CSR (compute_retrieval_self_join): coot_retrieval_join_count, _scan, coot_retrieval_join_fill per chunk
+of rows, the chunks sized by JOIN_TABLE_BYTES (_self_join).
 The searches on a prepared gallery share one host check (_check_search) and have one implementation per library call (_topk_few,
 _topk_tile, _topk_grouped, _topk_multi, _topk_scoped), which the public wrapper and the GalleryIndex method both call.
 GalleryIndex.add / update / compact: rows appended or overwritten in place together with their norms (coot_retrieval_rows_put),
@@ -34,7 +37,7 @@ import numpy as np
 from .retrieval_mirror import (VALKEYS, _ahead, _host_offsets, _labeled_metrics, compute_retrieval, compute_retrieval_cosine,  # noqa: F401
                                compute_retrieval_counts_part, compute_retrieval_labeled, compute_retrieval_topk, compute_retrieval_topk_grouped,
                                compute_retrieval_range, compute_retrieval_topk_masked, compute_retrieval_topk_multi, compute_retrieval_topk_scoped,
-                               strip_bounds)
+                               compute_retrieval_self_join, strip_bounds)
 
 
 def _ptr(t):
@@ -522,6 +525,106 @@ def retrieval_range_device(queries, gallery, norms, threshold, keep=None, max_re
     return _range(queries, gallery, norms, threshold, keep, max_results, order)
 
 
+# The self-join works through the gallery in chunks of rows; the table of block counts of one chunk (int32, rows x (blocks at or right
+# of the chunk's first block + 1)) holds at most this many bytes.  A chunk starts at a multiple of RETRIEVAL_RANGE_BLOCK rows and holds
+# at least that many, whatever the budget.  The result's bytes do not depend on it.  Read at call time.
+JOIN_TABLE_BYTES = 1 << 28
+_JOIN_ROWS_MAX = 65535 * 64 // RETRIEVAL_RANGE_BLOCK * RETRIEVAL_RANGE_BLOCK  # coot_retrieval_join_count: ceil(rows / 64) <= 65 535
+
+
+def _join_chunks(n: int, budget: int):
+    """The chunks [(row0, rows)] of a self-join of n rows under a table budget in bytes: row0 a multiple of 128, in order and covering
+    [0, n) once; as many rows as the chunk's table, rows x (ceil((n - row0) / 128) + 1) int32, fits the budget, in multiples of 128
+    and at least 128 (the last chunk: what is left).  Later chunks have narrower tables, so they are longer."""
+    blk = RETRIEVAL_RANGE_BLOCK
+    chunks, row0 = [], 0
+    while row0 < n:
+        stride = (n - row0 + blk - 1) // blk + 1
+        rows = min(max(blk, int(budget) // (4 * stride) // blk * blk), _JOIN_ROWS_MAX, n - row0)
+        chunks.append((row0, rows))
+        row0 += rows
+    return chunks
+
+
+def _self_join(gallery, norms, threshold, keep, groups, max_results, method=None, own_keep=None, count_only: bool = False):
+    """coot_retrieval_join_count / coot_retrieval_range_scan / coot_retrieval_join_fill per chunk of _join_chunks.  Checked in this
+    order: max_results, groups, keep, the threshold's type and shape, then where everything lives.  method, own_keep: the name and the
+    own filter of GalleryIndex.self_join / count_self_join; count_only: the counts after the scans, no fill."""
+    import torch
+    from . import lib as _lib
+    fn = "retrieval_self_join_device"
+    who = method or fn
+    if not count_only:
+        _check_range_result(who, max_results, "row")
+    assert gallery.dim() == 2, gallery.shape
+    n, d = gallery.shape
+    if groups is not None:
+        groups = _check_groups(who, groups, n, mirror=None)
+    if keep is not None:
+        keep = _check_keep(who, keep, n, mirror=None)
+    thr = _check_threshold(who, threshold, n)
+    _on_device(who, "compute_retrieval_self_join", gallery, norms, keep, groups)
+    code = _gallery_code(fn, gallery)
+    assert norms is None or (norms.dtype == torch.float32 and tuple(norms.shape) == (n,)), (norms.dtype, norms.shape, n)
+    gallery, norms, dev = gallery.contiguous(), None if norms is None else norms.contiguous(), gallery.device
+    if isinstance(thr, np.ndarray):
+        thr = torch.from_numpy(thr).to(dev)
+    elif thr.device != dev:
+        raise ValueError(f"{who}: threshold lives on {thr.device}, the gallery on {dev}")
+    thr = thr.contiguous()
+    keep = _and_own(own_keep, keep)
+    lib, st, blk = _lib.load(), _stream(), RETRIEVAL_RANGE_BLOCK
+    chunks = _join_chunks(n, JOIN_TABLE_BYTES)
+    table = torch.empty(max(r * ((n - r0 + blk - 1) // blk + 1) for r0, r in chunks), dtype=torch.int32, device=dev)  # the calls of a stream run in order: one table
+    counts = torch.empty(n, dtype=torch.int32, device=dev)
+    offsets = None if count_only else torch.empty(n + 1, dtype=torch.int64, device=dev)
+    if max_results is not None:
+        cap = int(max_results)
+        rows_out = torch.full((cap,), -1, dtype=torch.int32, device=dev)
+        scores_out = torch.full((cap,), float("-inf"), dtype=torch.float32, device=dev)
+    total, parts = 0, []
+    for row0, rows in chunks:
+        _lib.check(lib.coot_retrieval_join_count(gallery.data_ptr(), code, _ptr(norms), _ptr(keep), _ptr(groups), thr.data_ptr(), row0, rows, n, d,
+                                                 table.data_ptr(), st), "coot_retrieval_join_count")
+        # the first chunk's offsets are the result's; a later chunk's start at 0 and are shifted by what the chunks before it hold
+        off = None if count_only else offsets if row0 == 0 else torch.empty(rows + 1, dtype=torch.int64, device=dev)
+        _lib.check(lib.coot_retrieval_range_scan(table.data_ptr(), rows, n - row0, _ptr(off), counts[row0:].data_ptr(), st), "coot_retrieval_range_scan")
+        if count_only:
+            continue
+        if max_results is None:
+            cap = int(off[rows])  # (the synchronisation of this chunk)
+            rows_out = torch.empty(cap, dtype=torch.int32, device=dev)
+            scores_out = torch.empty(cap, dtype=torch.float32, device=dev)
+            parts.append((rows_out, scores_out))
+            if row0:
+                torch.add(off[1:], total, out=offsets[row0 + 1:row0 + rows + 1])
+            total += cap
+        elif row0:  # on the device: the running total is offsets[row0]
+            torch.add(off[1:], offsets[row0], out=offsets[row0 + 1:row0 + rows + 1])
+            off = offsets[row0:]
+        if cap:
+            _lib.check(lib.coot_retrieval_join_fill(gallery.data_ptr(), code, _ptr(norms), _ptr(keep), _ptr(groups), thr.data_ptr(), row0, rows, n, d,
+                                                    table.data_ptr(), off.data_ptr(), cap, rows_out.data_ptr(), scores_out.data_ptr(), st),
+                       "coot_retrieval_join_fill")
+    if count_only:
+        return counts
+    if max_results is None and len(parts) > 1:
+        rows_out, scores_out = torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+    return offsets, rows_out, scores_out
+
+
+def retrieval_self_join_device(gallery, norms, threshold, keep=None, groups=None, max_results=None):
+    """The self-join of a gallery as a prepared index holds it (coot_retrieval_join_count, coot_retrieval_range_scan,
+    coot_retrieval_join_fill): all pairs of rows at or above a threshold.  gallery cuda float32, bfloat16 or float16 [N, d], norms cuda
+    float32 [N] (GalleryIndex.norms) or None: rows used as they are.  threshold: a Python number, N numbers on the host or a cuda
+    torch.float32 tensor [N], as in retrieval_range_device; keep: cuda torch.bool or torch.uint8 [N]; groups: cuda torch.int32 or
+    torch.int64 [N] (int64 is converted once) or None.  Pair (i, j), i < j, is a hit when keep lets BOTH rows pass, groups is None or
+    groups[i] != groups[j], and s(i, j) >= threshold[i] in float32, s being the similarity the searches rank on with row i, widened
+    to float32, as the query.  Returns (offsets int64 [N + 1], rows int32 [T], scores float32 [T]) on the device: the CSR of
+    retrieval_range_device read as pairs — see GalleryIndex.self_join."""
+    return _self_join(gallery, norms, threshold, keep, groups, max_results)
+
+
 # retrieval_topk_multi_device: the table best [M][G] of one library call holds at most this many entries (2^25 x 8 bytes = 256 MiB); a
 # larger search runs as several calls, split where a paragraph ends, over one workspace.  One paragraph is never split: its own table
 # may reach the library's bound.
@@ -664,6 +767,8 @@ class GalleryIndex:
 
     Range search.  search_range(queries, threshold) returns every row at or above a query's threshold, however many, as CSR (offsets,
     rows, scores), and count_range their number: see the methods.  keep and the index's own filter apply as in search.
+    self_join(threshold) is the same question about the gallery itself: all pairs of rows at or above a threshold, each once;
+    count_self_join their number per row.
 
     Growth.  index.n (= len(index)) rows are searched, index.capacity rows fit the buffer; index.gallery, index.norms and index.keep
     are the first n rows of it, reassigned whenever n changes (a reference taken earlier keeps the rows it had).  capacity=None is the
@@ -956,6 +1061,36 @@ class GalleryIndex:
         sweep.  (The distractors that beat a ground truth: threshold = its score.)"""
         return _range(queries, self.gallery, self.norms if self.normalize else None, threshold, keep, None, "row",
                       method="GalleryIndex.count_range", own_keep=self.keep, count_only=True)
+
+    def self_join(self, threshold, keep=None, groups=None, max_results=None):
+        """The gallery against itself: ALL PAIRS of rows at or above a threshold (near-duplicate clips before a split is frozen):
+        (offsets int64 [N + 1], rows int32 [T], scores float32 [T]) on the device, the CSR of search_range read as pairs — the hits of
+        row i are the rows j > i, rows[offsets[i]:offsets[i + 1]], in ascending j, with the bytes of their scores; every unordered pair
+        appears once, under its smaller row.  The i of every pair: counts = offsets[1:] - offsets[:-1]; i =
+        torch.repeat_interleave(torch.arange(N, device=rows.device), counts, output_size=T).
+        threshold: a Python number, N numbers on the host or a cuda torch.float32 tensor [N], one per row.  Pair (i, j), i < j, is a
+        hit when keep (cuda torch.bool or torch.uint8 [N]) and the index's own filter (remove) let BOTH rows pass — a removed row
+        neither asks nor is returned, its segment is empty —, groups is None or groups[i] != groups[j] (cuda torch.int32 or
+        torch.int64 [N]: the video of a clip, so that the pairs are the near-duplicates ACROSS videos; the caller owns the table, as
+        in search_grouped), and s(i, j) >= threshold[i] in float32.  s is, bit for bit, the sim of search(gallery.float(), 1,
+        want_sim=True), and s(i, j) == s(j, i) on bytes; NaN, -0 and the infinities behave as in search_range.  Without groups, row
+        i's hits are those of search_range(gallery[i].float(), threshold[i], keep=keep) with j <= i dropped, when keep lets row i
+        pass: compute_retrieval_self_join of the similarities, byte for byte, for every storage type.
+        Both operands are read from the gallery as the index stores it and both norms are the index's: no float32 copy, no norm pass,
+        and the blocks left of the diagonal are not visited.  The rows are worked through in chunks whose table of block counts stays
+        under retrieval.JOIN_TABLE_BYTES (read at call time; chunks start at multiples of 128 rows and hold at least 128); the bytes
+        of the result do not depend on it.  max_results=None reads back one size per chunk and concatenates the chunks' results: one
+        synchronisation when the table fits in one chunk.  max_results=c >= 1 never synchronises: the offsets of a chunk are shifted on
+        the device by the running total, rows / scores have c entries, the first min(T, c) of the result and then -1 / -inf, and
+        offsets stay exact, so offsets[N] > c says that the result was cut.  Segments are in row order; there is no order= here."""
+        return _self_join(self.gallery, self.norms if self.normalize else None, threshold, keep, groups, max_results,
+                          method="GalleryIndex.self_join", own_keep=self.keep)
+
+    def count_self_join(self, threshold, keep=None, groups=None):
+        """How many pairs self_join would return per row, int32 [N] on the device: the count pass and the scan of every chunk, no
+        fill and no synchronisation.  Its sum is the number of pairs."""
+        return _self_join(self.gallery, self.norms if self.normalize else None, threshold, keep, groups, None,
+                          method="GalleryIndex.count_self_join", own_keep=self.keep, count_only=True)
 
     def neighbors(self, rows, k: int, groups=None, keep=None):
         """More like this: the k best rows for each of the index's own rows, (idx int32 [R, k], scores float32 [R, k]) on the device.

@@ -8,6 +8,7 @@ on a similarity matrix [M, N], M and N independent; under a keep flag per galler
 best row; the K best groups for a PARAGRAPH of queries (MaxSim), whose offsets _host_offsets checks for mirror and device wrappers
 alike; under a mask per QUERY, the rows with (only) or without (exclude) the id the query brings.
 compute_retrieval_range: every column at or above a row's threshold, however many, as CSR.
+compute_retrieval_self_join: the same on a gallery's similarities with itself, read as pairs: the columns right of the diagonal.
 compute_retrieval_labeled: ranks and metrics without the assumption "square, ground truth on the diagonal": labels[i] = the gallery
 row of query i; several queries per row, rows without a query and queries without a row (a label outside [0, N)) are allowed.
 strip_bounds / compute_retrieval_counts_part: one strip of rows of the sharded validation; the sum over the strips is the whole."""
@@ -156,6 +157,43 @@ def compute_retrieval_range(sim: np.ndarray, threshold, keep=None, order: str = 
     rows = np.concatenate(segs).astype(np.int32) if segs else np.zeros(0, np.int32)
     scores = np.concatenate([sim[i, c] for i, c in enumerate(segs)]) if segs else np.zeros(0, sim.dtype)
     return offsets, rows, scores.astype(sim.dtype)
+
+
+def compute_retrieval_self_join(sim: np.ndarray, threshold, keep=None, groups=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """All pairs of rows of a gallery at or above a threshold, from its similarities with itself, sim [N, N]: (offsets int64 [N + 1],
+    rows int32 [T], scores [T]), the CSR of compute_retrieval_range read as pairs — the hits of row i are the rows j > i, ascending,
+    with scores = sim[i, j]; every unordered pair appears once, under its smaller row.  threshold: one number or [N] numbers, rounded
+    to float32 once.  Pair (i, j), i < j, is a hit when keep (bytes or booleans [N], None: every row) lets BOTH rows pass (a row that
+    does not pass neither asks nor is returned: its segment is empty), groups is None or groups[i] != groups[j] (integers [N]), and
+    sim[i, j] >= threshold[i], the IEEE compare of compute_retrieval_range.  Row i is compute_retrieval_range(sim[i:i + 1],
+    threshold[i], keep=the rows j > i that are eligible for it)."""
+    sim = np.asarray(sim)
+    assert sim.ndim == 2 and sim.shape[0] == sim.shape[1], sim.shape
+    n = sim.shape[0]
+    with np.errstate(over="ignore"):
+        t = np.asarray(threshold).astype(np.float32)
+    assert t.shape in ((), (n,)), (t.shape, n)
+    t = np.broadcast_to(t, (n,))
+    ok = np.ones(n, bool)
+    if keep is not None:
+        keep = np.asarray(keep)
+        assert keep.shape == (n,), (keep.shape, n)
+        ok = keep != 0
+    if groups is not None:
+        groups = np.asarray(groups)
+        assert groups.shape == (n,) and groups.dtype.kind in "iu", (groups.shape, groups.dtype)
+    right = np.arange(n)
+    offsets = np.zeros(n + 1, np.int64)
+    rows, scores = [], []
+    for i in range(n):
+        el = ok & ok[i] & (right > i)
+        if groups is not None:
+            el &= groups != groups[i]
+        _, r, s = compute_retrieval_range(sim[i:i + 1], t[i], keep=el)
+        rows.append(r)
+        scores.append(s)
+        offsets[i + 1] = offsets[i] + len(r)
+    return offsets, np.concatenate(rows).astype(np.int32), np.concatenate(scores).astype(sim.dtype)
 
 
 def _host_offsets(fn: str, offsets, m: int, exc=ValueError) -> np.ndarray:

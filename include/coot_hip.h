@@ -591,6 +591,34 @@ int coot_retrieval_range_tile_fill(const float* queries, const void* gallery, in
                                    const float* thresholds, int M, int N, int d, const int32_t* block_base, const int64_t* offsets, int64_t capacity,
                                    int32_t* rows_out, float* scores_out, void* workspace, size_t workspace_bytes, coot_stream_t stream);
 
+/* ---- self-join: all pairs of gallery rows at or above a threshold ------------------------------------------------------------------
+ * The tile range search with the gallery on both sides.  Pair (i, j), i < j, is a hit when keep (NULL: no filter) lets BOTH rows pass,
+ * groups is NULL or groups[i] != groups[j] (device int32 [N] as in coot_retrieval_topk_scoped, integer compare), and
+ * s(i, j) >= thresholds[i], the IEEE fp32 compare of the range search.  s(i, j) is the fp32 chain of every search here with row i as the
+ * query: the stored row widened (exact) and gallery_norms[i] as its norm, which is the norm of the widened row — so the bits are those
+ * of coot_retrieval_range_tile_count / _fill on a float32 copy of the gallery, and s(i, j) == s(j, i).  Every unordered pair appears
+ * once, under its smaller row, rows ascending: the CSR of the range search read as pairs.
+ * A call serves the rows [row0, row0 + rows), row0 a multiple of COOT_RETRIEVAL_RANGE_BLOCK, rows >= 1, row0 + rows <= N,
+ * ceil(rows / 64) <= 65535.  thresholds: device fp32 [N], indexed by the absolute row.  block_counts: int32
+ * [rows][COOT_RETRIEVAL_RANGE_TABLE_ROW(N - row0)], one slot per block at or right of the chunk's first block — the table of a
+ * gallery of N - row0 rows:
+ *   coot_retrieval_join_count writes the first ceil(N / 128) - row0 / 128 entries of every row; the slots left of the diagonal are
+ *     zeros and their blocks are not read, nor is a block in which keep leaves no row.
+ *   coot_retrieval_range_scan(block_counts, rows, N - row0, offsets, counts_out, stream), unchanged.
+ *   coot_retrieval_join_fill: the count call's arguments again, block_base = the scanned table, offsets = int64 [rows], the position of
+ *     the first hit of row row0 + r at offsets[r] (the scan's, or the scan's shifted by what earlier chunks hold), and rows_out /
+ *     scores_out with room for `capacity` entries: a hit whose position is below capacity is written, the others are not, and entries
+ *     that no hit claims are not touched.  A block in which none of a workgroup's 64 rows has a hit is not read.
+ * No workspace: the index's norms serve both sides.  No atomic touches global memory: the bytes do not depend on the schedule or on
+ * how the rows are cut into chunks.  A refused call (unknown dtype, a null pointer other than gallery_norms, keep and groups, row0 or
+ * rows outside their range, N or d < 1, capacity < 0) returns before any launch and writes nothing.  No allocation, no synchronisation;
+ * no pointer is retained. */
+int coot_retrieval_join_count(const void* gallery, int gallery_dtype, const float* gallery_norms, const uint8_t* keep, const int32_t* groups,
+                              const float* thresholds, int row0, int rows, int N, int d, int32_t* block_counts, coot_stream_t stream);
+int coot_retrieval_join_fill(const void* gallery, int gallery_dtype, const float* gallery_norms, const uint8_t* keep, const int32_t* groups,
+                             const float* thresholds, int row0, int rows, int N, int d, const int32_t* block_base, const int64_t* offsets,
+                             int64_t capacity, int32_t* rows_out, float* scores_out, coot_stream_t stream);
+
 /* ---- a prepared gallery that changes: rows written in place, their norms with them ---------------------------------------
  * coot_retrieval_rows_put writes the R rows of src [R, d] into the buffer gallery [N, d] and, where norms != NULL, norms[row] of
  * every row it wrote: what a corpus that grows (rows appended into spare capacity) or is re-encoded (rows overwritten) needs,
