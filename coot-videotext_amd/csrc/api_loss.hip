@@ -158,6 +158,31 @@ int coot_gemm_nt(const void* X, int64_t ldx, const void* W, int64_t ldw, int M, 
   g.epi.out_f32 = out_f32;
   return launch_gemm_nt(g, (hipStream_t)stream);
 }
+// tests: the descriptor as the networks fill it (api.hip), dropout threshold and scale by mkdrop's arithmetic
+int coot_debug_gemm_nt(const coot_gemm_nt_args* a, coot_stream_t stream) {
+  COOT_REQUIRE(a, "debug_gemm_nt: null arguments");
+  COOT_REQUIRE(!a->pe || (a->pe_L > 0 && a->pe_L2 > 0), "debug_gemm_nt: pe_L / pe_L2 must be positive");
+  COOT_REQUIRE(a->act != 2 || a->aux, "debug_gemm_nt: act 2 needs aux");
+  COOT_REQUIRE(!(a->p > 0.f) || a->drop_ld % 2 == 0, "debug_gemm_nt: drop_ld must be even");
+  GemmNT g; g.X = (const bf16_t*)a->X; g.ldx = a->ldx; g.W = (const bf16_t*)a->W; g.ldw = a->ldw; g.M = a->M; g.N = a->N; g.K = a->K;
+  g.groups = a->groups > 0 ? a->groups : 1; g.zX = a->zX; g.zW = a->zW; g.zOut = a->zOut;
+  GemmEpi& e = g.epi;
+  e.bias = a->bias; e.act = a->act; e.aux = (const bf16_t*)a->aux; e.ldaux = a->ldaux; e.save_pre = (bf16_t*)a->save_pre; e.ldpre = a->ldpre;
+  e.res = (const bf16_t*)a->res; e.ldres = a->ldres; e.colsum = a->colsum;
+  if (a->pe) { e.pe = a->pe; e.pe_L = a->pe_L; e.pe_T0 = a->pe_T0; e.pe_L2 = a->pe_L2; }
+  if (a->p > 0.f) {
+    const double t = (double)a->p * 4294967296.0;
+    e.drop_thr = t >= 4294967295.0 ? 4294967295u : (unsigned)t;
+    if (e.drop_thr < 65536u) e.drop_thr = 65536u;
+    e.drop_inv_keep = (float)(1.0 / (1.0 - (double)(e.drop_thr >> 16) / 65536.0));
+    e.drop_seed = a->seed; e.drop_site = a->site; e.drop_ld = a->drop_ld;
+  }
+  e.out = a->out; e.ldc = a->ldc; e.out_f32 = a->out_f32;
+  if (a->part_ws) set_partials_workspace(a->part_ws, a->part_ws_floats);
+  const int rc = launch_gemm_nt(g, (hipStream_t)stream);
+  if (a->part_ws) set_partials_workspace(nullptr, 0);
+  return rc;
+}
 size_t coot_gemm_tn_workspace_bytes(int T, int Mo, int No) { return gemm_tn_workspace_floats(T, Mo, No, 1) * sizeof(float); }
 int coot_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, int T, int Mo, int No, float* C, int64_t ldc,
                  void* workspace, size_t workspace_bytes, coot_stream_t stream) {

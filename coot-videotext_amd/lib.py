@@ -27,7 +27,7 @@ EXPORTS = [
     "coot_net_param_info", "coot_net_out_dim", "coot_net_wpack_bytes", "coot_net_pack_weights", "coot_nets_pack_weights",
     "coot_net_saved_bytes", "coot_net_scratch_bytes", "coot_net_fwd", "coot_net_bwd", "coot_net_grads_overwrite", "coot_nets_zero_grads", "coot_nets_zero_grads_ex", "coot_debug_written_matrices", "coot_pack_fwd",
     "coot_pack_bwd", "coot_contrastive_scratch_bytes", "coot_contrastive_fwd_bwd", "coot_contrastive_fwd_bwd_part", "coot_contrastive_f32_scratch_bytes", "coot_contrastive_fwd_bwd_f32", "coot_cyclecons_fwd_bwd",
-    "coot_gemm_nt", "coot_gemm_tn", "coot_gemm_tn_batch", "coot_debug_tn_xcd_map", "coot_debug_clock_monitor", "coot_gemm_tn_workspace_bytes", "coot_ln_fwd", "coot_attn_fwd", "coot_probe_tr16", "coot_timing_enable",
+    "coot_gemm_nt", "coot_debug_gemm_nt", "coot_gemm_tn", "coot_gemm_tn_batch", "coot_debug_tn_xcd_map", "coot_debug_clock_monitor", "coot_gemm_tn_workspace_bytes", "coot_ln_fwd", "coot_attn_fwd", "coot_probe_tr16", "coot_timing_enable",
     "coot_timing_collect", "coot_step_workspace_bytes", "coot_train_step", "coot_step_forward", "coot_step_backward",
     "coot_adam_step", "coot_radam_step", "coot_step_update", "coot_step_set_global_done_events", "coot_step_device_state_bytes", "coot_step_set_device_state", "coot_step_loss_scaler_bytes", "coot_step_set_loss_scaler", "coot_step_unscale_grads", "coot_step_grad_clip_bytes", "coot_step_set_grad_clip", "coot_step_grad_norm", "coot_collate_level", "coot_collate_packed", "coot_sample_cycle_indices", "coot_step_set_cycle_indices", "coot_step_input_stage_bytes", "coot_step_set_input_stages", "coot_step_set_next_batch", "coot_contrastive_fwd_bwd_dp", "coot_contrastive_fwd_bwd_dp_blocks", "coot_retrieval_workspace_bytes", "coot_retrieval_ranks", "coot_retrieval_topk_workspace_bytes", "coot_retrieval_topk",
     "coot_retrieval_ranks_part_workspace_bytes", "coot_retrieval_ranks_part", "coot_retrieval_metrics",
@@ -88,6 +88,16 @@ class TnProblem(C.Structure):
     _fields_ = [("A", C.c_void_p), ("lda", C.c_int64), ("B", C.c_void_p), ("ldb", C.c_int64), ("T", C.c_int), ("Mo", C.c_int),
                 ("No", C.c_int), ("C", C.c_void_p), ("ldc", C.c_int64), ("a_colsum", C.c_void_p), ("overwrite", C.c_int),
                 ("groups", C.c_int), ("zA", C.c_int64), ("zB", C.c_int64), ("zC", C.c_int64)]
+
+
+class GemmNtArgs(C.Structure):
+    """coot_gemm_nt_args: the whole gemm_nt descriptor (grouping, fused epilogue, dropout) for coot_debug_gemm_nt."""
+    _fields_ = [("X", C.c_void_p), ("ldx", C.c_int64), ("W", C.c_void_p), ("ldw", C.c_int64), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
+                ("groups", C.c_int), ("zX", C.c_int64), ("zW", C.c_int64), ("zOut", C.c_int64),
+                ("bias", C.c_void_p), ("act", C.c_int), ("aux", C.c_void_p), ("ldaux", C.c_int64), ("save_pre", C.c_void_p), ("ldpre", C.c_int64),
+                ("res", C.c_void_p), ("ldres", C.c_int64), ("pe", C.c_void_p), ("pe_L", C.c_int), ("pe_T0", C.c_int), ("pe_L2", C.c_int),
+                ("colsum", C.c_void_p), ("p", C.c_float), ("seed", C.c_uint64), ("site", C.c_uint), ("drop_ld", C.c_int64),
+                ("out", C.c_void_p), ("ldc", C.c_int64), ("out_f32", C.c_int), ("part_ws", C.c_void_p), ("part_ws_floats", C.c_size_t)]
 
 
 class PackedSeqs(C.Structure):
@@ -248,6 +258,7 @@ def load():
     lib.coot_stream_destroy.argtypes = [vp]
     lib.coot_streams_overlap.argtypes = [vp, vp]
     lib.coot_gemm_nt.argtypes = [vp, i64, vp, i64, i32, i32, i32, vp, i32, vp, i64, vp, i64, i32, vp]
+    lib.coot_debug_gemm_nt.argtypes = [C.POINTER(GemmNtArgs), vp]
     lib.coot_gemm_tn.argtypes = [vp, i64, vp, i64, i32, i32, i32, vp, i64, vp, sz, vp]
     lib.coot_gemm_tn_batch.argtypes = [C.POINTER(TnProblem), i32, vp, sz, vp, vp]
     ip = C.POINTER(i32)

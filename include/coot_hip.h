@@ -927,6 +927,31 @@ int coot_radam_step(float* params, const float* grads, float* m, float* v, const
 int coot_gemm_nt(const void* X, int64_t ldx, const void* W, int64_t ldw, int M, int N, int K, const float* bias,
                  int act, const void* residual_bf16, int64_t ldres, void* out, int64_t ldc, int out_f32,
                  coot_stream_t stream);
+/* The whole gemm_nt descriptor the networks use (tests): every launch variant, grouped launches and the full fused epilogue.
+ * Per element, in this order: v = acc + bias; v *= dropout scale (act 0/1); save_pre = bf16(v); act 1: v = gelu(v);
+ * v += pe[pos][col] (pos = row % pe_L for rows < pe_T0, else (row - pe_T0) % pe_L2; pe has N columns); v += res;
+ * act 2: v *= gelu'(aux) * dropout scale; out = v; colsum[col] += v.  Group z (blockIdx.z) reads X + z*zX, W + z*zW and
+ * addresses bias / aux / save_pre / res / colsum / out at column z*zOut + col.  Dropout (p > 0): the mask of (seed, site) at
+ * element index row*drop_ld + z*zOut + col, p quantised as coot_debug_dropout_scales does.  part_ws (optional, device fp32,
+ * ceil(M/64) * max(N, groups*zOut) floats): the column sums of the M > 512 kernels go through per-row-block partials and one
+ * reduction, as inside a network call; without it they are added with atomics.  M, ld*, z* in elements; N, K, ld*, z* % 8 == 0. */
+typedef struct coot_gemm_nt_args {
+  const void* X; int64_t ldx;   /* bf16 [M, K] */
+  const void* W; int64_t ldw;   /* bf16 [N, K] */
+  int M, N, K;
+  int groups; int64_t zX, zW, zOut;
+  const float* bias;            /* fp32 [groups*zOut] or NULL */
+  int act;                      /* 0 none | 1 gelu | 2 multiply by gelu'(aux) */
+  const void* aux; int64_t ldaux;
+  void* save_pre; int64_t ldpre;
+  const void* res; int64_t ldres;
+  const float* pe; int pe_L, pe_T0, pe_L2;
+  float* colsum;
+  float p; uint64_t seed; unsigned site; int64_t drop_ld;
+  void* out; int64_t ldc; int out_f32;
+  float* part_ws; size_t part_ws_floats;
+} coot_gemm_nt_args;
+int coot_debug_gemm_nt(const coot_gemm_nt_args* a, coot_stream_t stream);
 /* C[Mo,No] fp32 += sum_t A[t,Mo] * B[t,No].  workspace (coot_gemm_tn_workspace_bytes) selects the two-pass
  * split reduction; NULL falls back to fp32 atomics. */
 size_t coot_gemm_tn_workspace_bytes(int T, int Mo, int No);
