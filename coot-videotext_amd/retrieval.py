@@ -22,6 +22,9 @@ coot_retrieval_range_tile_count, _scan, _tile_fill from there on, one call per p
 retrieval_self_join_device / GalleryIndex.self_join, count_self_join: the gallery against itself, all pairs (i, j), i < j, at or above
 row i's threshold, as the same CSR (compute_retrieval_self_join): coot_retrieval_join_count, _scan, coot_retrieval_join_fill per chunk
 of rows, the chunks sized by JOIN_TABLE_BYTES (_self_join).
+retrieval_join_device / GalleryIndex.join, count_join: the rows of one index against the rows of another, all pairs at or above the
+left row's threshold, as the same CSR (compute_retrieval_join): coot_retrieval_cross_join_count, _scan, coot_retrieval_cross_join_fill
+per chunk of left rows, under the same budget (_cross_join).
 The searches on a prepared gallery share one host check (_check_search) and have one implementation per library call (_topk_few,
 _topk_tile, _topk_grouped, _topk_multi, _topk_scoped), which the public wrapper and the GalleryIndex method both call.
 GalleryIndex.add / update / compact: rows appended or overwritten in place together with their norms (coot_retrieval_rows_put),
@@ -37,7 +40,7 @@ import numpy as np
 from .retrieval_mirror import (VALKEYS, _ahead, _host_offsets, _labeled_metrics, compute_retrieval, compute_retrieval_cosine,  # noqa: F401
                                compute_retrieval_counts_part, compute_retrieval_labeled, compute_retrieval_topk, compute_retrieval_topk_grouped,
                                compute_retrieval_range, compute_retrieval_topk_masked, compute_retrieval_topk_multi, compute_retrieval_topk_scoped,
-                               compute_retrieval_self_join, strip_bounds)
+                               compute_retrieval_self_join, compute_retrieval_join, strip_bounds)
 
 
 def _ptr(t):
@@ -625,6 +628,124 @@ def retrieval_self_join_device(gallery, norms, threshold, keep=None, groups=None
     return _self_join(gallery, norms, threshold, keep, groups, max_results)
 
 
+_CROSS_JOIN_TILE = 64  # coot_retrieval_cross_join_count: the row tile; a chunk of left rows starts at a multiple of it
+_CROSS_JOIN_ROWS_MAX = 65535 * _CROSS_JOIN_TILE  # ceil(rows / 64) <= 65 535
+
+
+def _cross_join_chunks(n_left: int, n_right: int, budget: int):
+    """The chunks [(row0, rows)] of left rows of a join of n_left rows with n_right rows under a table budget in bytes: row0 a
+    multiple of 64, in order and covering [0, n_left) once; as many rows as the chunk's table, rows x (ceil(n_right / 128) + 1) int32,
+    fits the budget, in multiples of 64 and at least 64 (the last chunk: what is left).  Every chunk's table has the same width."""
+    tile = _CROSS_JOIN_TILE
+    stride = (n_right + RETRIEVAL_RANGE_BLOCK - 1) // RETRIEVAL_RANGE_BLOCK + 1
+    per = min(max(tile, int(budget) // (4 * stride) // tile * tile), _CROSS_JOIN_ROWS_MAX)
+    return [(row0, min(per, n_left - row0)) for row0 in range(0, n_left, per)]
+
+
+def _cross_join(left, left_norms, right, right_norms, threshold, keep, other_keep, groups, other_groups, max_results, method=None,
+                own_keep=None, other_own_keep=None, count_only: bool = False):
+    """coot_retrieval_cross_join_count / coot_retrieval_range_scan / coot_retrieval_cross_join_fill per chunk of _cross_join_chunks.
+    Checked in this order: max_results, the widths, both norms or none, one device for both sides, groups, keep, the threshold's
+    type and shape, then where everything lives.  method, own_keep, other_own_keep: the name and the own filters of GalleryIndex.join / count_join; count_only:
+    the counts after the scans, no fill."""
+    import torch
+    from . import lib as _lib
+    fn = "retrieval_join_device"
+    who = method or fn
+    if not count_only:
+        _check_range_result(who, max_results, "row")
+    assert left.dim() == 2 and right.dim() == 2, (left.shape, right.shape)
+    (nl, d), nr = left.shape, right.shape[0]
+    if right.shape[1] != d:
+        raise ValueError(f"{who}: left rows of width {d}, right rows of width {right.shape[1]}")
+    if (left_norms is None) != (right_norms is None):
+        raise ValueError(f"{who}: one side brings row norms and the other does not (one similarity needs both norms or none)")
+    if right.device != left.device:
+        raise ValueError(f"{who}: the right rows live on {right.device}, the left rows on {left.device}")
+    if (groups is None) != (other_groups is None):
+        raise ValueError(f"{who}: groups and other_groups are given together or not at all (ids of one space, compared by inequality)")
+    if groups is not None:
+        groups = _check_groups(who, groups, nl, mirror=None)
+        other_groups = _check_groups(who, other_groups, nr, mirror=None)
+    if keep is not None:
+        keep = _check_keep(who, keep, nl, mirror=None)
+    if other_keep is not None:
+        other_keep = _check_keep(who, other_keep, nr, mirror=None)
+    thr = _check_threshold(who, threshold, nl)
+    _on_device(who, "compute_retrieval_join", left, left_norms, right, right_norms, keep, other_keep, groups, other_groups)
+    dev = left.device
+    for name, t in (("the right norms", right_norms), ("keep", keep), ("other_keep", other_keep), ("groups", groups),
+                    ("other_groups", other_groups), ("the left norms", left_norms)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"{who}: {name} live on {t.device}, the left rows on {dev}")
+    lcode, rcode = _gallery_code(fn, left), _gallery_code(fn, right)
+    for norms, n in ((left_norms, nl), (right_norms, nr)):
+        assert norms is None or (norms.dtype == torch.float32 and tuple(norms.shape) == (n,)), (norms.dtype, norms.shape, n)
+    left, right = left.contiguous(), right.contiguous()
+    if left_norms is not None:
+        left_norms, right_norms = left_norms.contiguous(), right_norms.contiguous()
+    if isinstance(thr, np.ndarray):
+        thr = torch.from_numpy(thr).to(dev)
+    elif thr.device != dev:
+        raise ValueError(f"{who}: threshold lives on {thr.device}, the left rows on {dev}")
+    thr = thr.contiguous()
+    keep, other_keep = _and_own(own_keep, keep), _and_own(other_own_keep, other_keep)
+    lib, st = _lib.load(), _stream()
+    stride = (nr + RETRIEVAL_RANGE_BLOCK - 1) // RETRIEVAL_RANGE_BLOCK + 1
+    chunks = _cross_join_chunks(nl, nr, JOIN_TABLE_BYTES)
+    table = torch.empty(max(r for _, r in chunks) * stride, dtype=torch.int32, device=dev)  # the calls of a stream run in order: one table
+    counts = torch.empty(nl, dtype=torch.int32, device=dev)
+    offsets = None if count_only else torch.empty(nl + 1, dtype=torch.int64, device=dev)
+    if max_results is not None:
+        cap = int(max_results)
+        rows_out = torch.full((cap,), -1, dtype=torch.int32, device=dev)
+        scores_out = torch.full((cap,), float("-inf"), dtype=torch.float32, device=dev)
+    head = (left.data_ptr(), lcode, _ptr(left_norms), right.data_ptr(), rcode, _ptr(right_norms), _ptr(keep), _ptr(other_keep), _ptr(groups),
+            _ptr(other_groups), thr.data_ptr())
+    total, parts = 0, []
+    for row0, rows in chunks:
+        _lib.check(lib.coot_retrieval_cross_join_count(*head, row0, rows, nl, nr, d, table.data_ptr(), st), "coot_retrieval_cross_join_count")
+        # the first chunk's offsets are the result's; a later chunk's start at 0 and are shifted by what the chunks before it hold
+        off = None if count_only else offsets if row0 == 0 else torch.empty(rows + 1, dtype=torch.int64, device=dev)
+        _lib.check(lib.coot_retrieval_range_scan(table.data_ptr(), rows, nr, _ptr(off), counts[row0:].data_ptr(), st), "coot_retrieval_range_scan")
+        if count_only:
+            continue
+        if max_results is None:
+            cap = int(off[rows])  # (the synchronisation of this chunk)
+            rows_out = torch.empty(cap, dtype=torch.int32, device=dev)
+            scores_out = torch.empty(cap, dtype=torch.float32, device=dev)
+            parts.append((rows_out, scores_out))
+            if row0:
+                torch.add(off[1:], total, out=offsets[row0 + 1:row0 + rows + 1])
+            total += cap
+        elif row0:  # on the device: the running total is offsets[row0]
+            torch.add(off[1:], offsets[row0], out=offsets[row0 + 1:row0 + rows + 1])
+            off = offsets[row0:]
+        if cap:
+            _lib.check(lib.coot_retrieval_cross_join_fill(*head, row0, rows, nl, nr, d, table.data_ptr(), off.data_ptr(), cap, rows_out.data_ptr(),
+                                                          scores_out.data_ptr(), st), "coot_retrieval_cross_join_fill")
+    if count_only:
+        return counts
+    if max_results is None and len(parts) > 1:
+        rows_out, scores_out = torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+    return offsets, rows_out, scores_out
+
+
+def retrieval_join_device(left_gallery, left_norms, right_gallery, right_norms, threshold, keep=None, other_keep=None, groups=None,
+                          other_groups=None, max_results=None):
+    """The join of two galleries as prepared indexes hold them (coot_retrieval_cross_join_count, coot_retrieval_range_scan,
+    coot_retrieval_cross_join_fill): all pairs (left row, right row) at or above the left row's threshold.  left_gallery [N_left, d],
+    right_gallery [N_right, d]: cuda float32, bfloat16 or float16, each its own; left_norms / right_norms: cuda float32 [N_left] /
+    [N_right] (GalleryIndex.norms), or both None: rows used as they are (one without the other is a ValueError).  threshold: a
+    Python number, N_left numbers on the host or a cuda torch.float32 tensor [N_left], as in retrieval_range_device; keep /
+    other_keep: cuda torch.bool or torch.uint8 [N_left] / [N_right]; groups / other_groups: cuda torch.int32 or torch.int64 [N_left]
+    / [N_right] (int64 is converted once), both or neither.  Pair (i, j) is a hit when keep lets left row i pass, other_keep right
+    row j, the groups are None or groups[i] != other_groups[j], and s(i, j) >= threshold[i] in float32, s being the similarity the
+    searches rank on with left row i, widened to float32, as the query.  Returns (offsets int64 [N_left + 1], rows int32 [T], scores
+    float32 [T]) on the device: the CSR of retrieval_range_device read as pairs — see GalleryIndex.join."""
+    return _cross_join(left_gallery, left_norms, right_gallery, right_norms, threshold, keep, other_keep, groups, other_groups, max_results)
+
+
 # retrieval_topk_multi_device: the table best [M][G] of one library call holds at most this many entries (2^25 x 8 bytes = 256 MiB); a
 # larger search runs as several calls, split where a paragraph ends, over one workspace.  One paragraph is never split: its own table
 # may reach the library's bound.
@@ -768,7 +889,8 @@ class GalleryIndex:
     Range search.  search_range(queries, threshold) returns every row at or above a query's threshold, however many, as CSR (offsets,
     rows, scores), and count_range their number: see the methods.  keep and the index's own filter apply as in search.
     self_join(threshold) is the same question about the gallery itself: all pairs of rows at or above a threshold, each once;
-    count_self_join their number per row.
+    count_self_join their number per row.  join(right, threshold) asks it about two indexes: all pairs (row of this index, row of
+    right) at or above a threshold, with a filter and group ids on either side; count_join their number per left row.
 
     Growth.  index.n (= len(index)) rows are searched, index.capacity rows fit the buffer; index.gallery, index.norms and index.keep
     are the first n rows of it, reassigned whenever n changes (a reference taken earlier keeps the rows it had).  capacity=None is the
@@ -1091,6 +1213,54 @@ class GalleryIndex:
         fill and no synchronisation.  Its sum is the number of pairs."""
         return _self_join(self.gallery, self.norms if self.normalize else None, threshold, keep, groups, None,
                           method="GalleryIndex.count_self_join", own_keep=self.keep, count_only=True)
+
+    def _join(self, who: str, other, threshold, keep, other_keep, groups, other_groups, max_results, count_only: bool):
+        """join / count_join: what two indexes have to share, then _cross_join on what they hold."""
+        if not isinstance(other, GalleryIndex):
+            raise TypeError(f"{who}: the right side has to be a GalleryIndex, not {type(other).__name__}")
+        if other.gallery.shape[1] != self.gallery.shape[1]:
+            raise ValueError(f"{who}: this index holds rows of width {self.gallery.shape[1]}, the right one of width {other.gallery.shape[1]}")
+        if self.normalize != other.normalize:
+            raise ValueError(f"{who}: this index has normalize={self.normalize}, the right one normalize={other.normalize} "
+                             "(one similarity needs both norms or none)")
+        if other.gallery.device != self.gallery.device:
+            raise ValueError(f"{who}: this index lives on {self.gallery.device}, the right one on {other.gallery.device}")
+        return _cross_join(self.gallery, self.norms if self.normalize else None, other.gallery, other.norms if other.normalize else None,
+                           threshold, keep, other_keep, groups, other_groups, max_results, method=who, own_keep=self.keep,
+                           other_own_keep=other.keep, count_only=count_only)
+
+    def join(self, right, threshold, keep=None, other_keep=None, groups=None, other_groups=None, max_results=None):
+        """This index against ANOTHER one: all pairs (row i of this index, row j of `right`) at or above a threshold (does the
+        validation split leak into the training split; which rows of an upload the resident corpus already holds): (offsets int64
+        [N_left + 1], rows int32 [T], scores float32 [T]) on the device, the CSR of search_range read as pairs — the hits of left
+        row i are rows[offsets[i]:offsets[i + 1]], rows of `right` in ascending order, with the bytes of their scores.  The i of
+        every pair: counts = offsets[1:] - offsets[:-1]; i = torch.repeat_interleave(torch.arange(N_left, device=rows.device),
+        counts, output_size=T).
+        threshold: a Python number, N_left numbers on the host or a cuda torch.float32 tensor [N_left], one per left row.  Pair
+        (i, j) is a hit when keep (cuda torch.bool or torch.uint8 [N_left]) and this index's own filter (remove) let row i pass — a
+        removed left row does not ask, its segment is empty —, other_keep ([N_right]) and right's own filter let row j pass, groups
+        and other_groups are both None or groups[i] != other_groups[j] (cuda torch.int32 or torch.int64 [N_left] and [N_right] in one
+        id space: the source video of a clip, so that clips of one video in both splits are no leak; the caller owns the tables, as
+        in search_grouped; exactly one of them is a ValueError), and s(i, j) >= threshold[i] in float32.  s is, bit for bit, the sim
+        of right.search(self.gallery.float(), 1, want_sim=True); NaN, -0 and the infinities behave as in search_range.  Without
+        groups, row i's hits are those of right.search_range(self.gallery[i].float(), threshold[i], keep=other_keep) when the left
+        filters let row i pass: compute_retrieval_join of the similarities, byte for byte, for all nine pairs of storage types.
+        Both operands are read as their index stores them and both norms are the stored ones: no float32 copy of the left side and
+        no norm pass.  `right` has to be a GalleryIndex of the same width, the same normalize and on the same device (TypeError /
+        ValueError before anything is launched); right may be this index itself, which returns both orientations and the diagonal.
+        The left rows are worked through in chunks whose table of block counts, rows x (ceil(N_right / 128) + 1) int32, stays under
+        retrieval.JOIN_TABLE_BYTES (read at call time; chunks start at multiples of 64 rows and hold at least 64); the bytes of the
+        result do not depend on it.  max_results=None reads back one size per chunk and concatenates the chunks' results: one
+        synchronisation when the table fits in one chunk.  max_results=c >= 1 never synchronises: the offsets of a chunk are
+        shifted on the device by the running total, rows / scores have c entries, the first min(T, c) of the result and then
+        -1 / -inf, and offsets stay exact, so offsets[N_left] > c says that the result was cut.  Segments are in row order; there
+        is no order= here."""
+        return self._join("GalleryIndex.join", right, threshold, keep, other_keep, groups, other_groups, max_results, False)
+
+    def count_join(self, right, threshold, keep=None, other_keep=None, groups=None, other_groups=None):
+        """How many pairs join would return per left row, int32 [N_left] on the device: the count pass and the scan of every chunk,
+        no fill and no synchronisation.  Its sum is the number of pairs."""
+        return self._join("GalleryIndex.count_join", right, threshold, keep, other_keep, groups, other_groups, None, True)
 
     def neighbors(self, rows, k: int, groups=None, keep=None):
         """More like this: the k best rows for each of the index's own rows, (idx int32 [R, k], scores float32 [R, k]) on the device.

@@ -9,6 +9,7 @@ best row; the K best groups for a PARAGRAPH of queries (MaxSim), whose offsets _
 alike; under a mask per QUERY, the rows with (only) or without (exclude) the id the query brings.
 compute_retrieval_range: every column at or above a row's threshold, however many, as CSR.
 compute_retrieval_self_join: the same on a gallery's similarities with itself, read as pairs: the columns right of the diagonal.
+compute_retrieval_join: the same on the similarities of two galleries, with a filter and group ids on either side.
 compute_retrieval_labeled: ranks and metrics without the assumption "square, ground truth on the diagonal": labels[i] = the gallery
 row of query i; several queries per row, rows without a query and queries without a row (a label outside [0, N)) are allowed.
 strip_bounds / compute_retrieval_counts_part: one strip of rows of the sharded validation; the sum over the strips is the whole."""
@@ -189,6 +190,51 @@ def compute_retrieval_self_join(sim: np.ndarray, threshold, keep=None, groups=No
         el = ok & ok[i] & (right > i)
         if groups is not None:
             el &= groups != groups[i]
+        _, r, s = compute_retrieval_range(sim[i:i + 1], t[i], keep=el)
+        rows.append(r)
+        scores.append(s)
+        offsets[i + 1] = offsets[i] + len(r)
+    return offsets, np.concatenate(rows).astype(np.int32), np.concatenate(scores).astype(sim.dtype)
+
+
+def compute_retrieval_join(sim: np.ndarray, threshold, keep=None, other_keep=None, groups=None,
+                           other_groups=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """All pairs (row of a left gallery, row of a right one) at or above a threshold, from their similarities sim [M, N]: (offsets
+    int64 [M + 1], rows int32 [T], scores [T]), the CSR of compute_retrieval_range read as pairs — the hits of left row i are the
+    right rows rows[offsets[i]:offsets[i + 1]], ascending, with scores = sim[i, rows].  threshold: one number or [M] numbers, rounded
+    to float32 once.  Pair (i, j) is a hit when keep (bytes or booleans [M], None: every row) lets left row i pass (a row that does
+    not pass does not ask: its segment is empty), other_keep ([N]) lets right row j pass, groups and other_groups are both None or
+    groups[i] != other_groups[j] (integers [M] and [N] in one id space; exactly one of them is an error), and sim[i, j] >=
+    threshold[i], the IEEE compare of compute_retrieval_range.  Without filters it is compute_retrieval_range(sim, threshold)."""
+    sim = np.asarray(sim)
+    assert sim.ndim == 2, sim.shape
+    m, n = sim.shape
+    with np.errstate(over="ignore"):
+        t = np.asarray(threshold).astype(np.float32)
+    assert t.shape in ((), (m,)), (t.shape, m)
+    t = np.broadcast_to(t, (m,))
+    ask, ok = np.ones(m, bool), np.ones(n, bool)
+    if keep is not None:
+        keep = np.asarray(keep)
+        assert keep.shape == (m,), (keep.shape, m)
+        ask = keep != 0
+    if other_keep is not None:
+        other_keep = np.asarray(other_keep)
+        assert other_keep.shape == (n,), (other_keep.shape, n)
+        ok = other_keep != 0
+    if (groups is None) != (other_groups is None):
+        raise ValueError("compute_retrieval_join: groups and other_groups are given together or not at all")
+    if groups is not None:
+        groups, other_groups = np.asarray(groups), np.asarray(other_groups)
+        assert groups.shape == (m,) and groups.dtype.kind in "iu", (groups.shape, groups.dtype)
+        assert other_groups.shape == (n,) and other_groups.dtype.kind in "iu", (other_groups.shape, other_groups.dtype)
+        groups, other_groups = groups.astype(np.int64), other_groups.astype(np.int64)
+    offsets = np.zeros(m + 1, np.int64)
+    rows, scores = [np.zeros(0, np.int32)], [np.zeros(0, sim.dtype)]
+    for i in range(m):
+        el = ok & ask[i]
+        if groups is not None:
+            el = el & (other_groups != groups[i])
         _, r, s = compute_retrieval_range(sim[i:i + 1], t[i], keep=el)
         rows.append(r)
         scores.append(s)

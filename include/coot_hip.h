@@ -619,6 +619,39 @@ int coot_retrieval_join_fill(const void* gallery, int gallery_dtype, const float
                              const float* thresholds, int row0, int rows, int N, int d, const int32_t* block_base, const int64_t* offsets,
                              int64_t capacity, int32_t* rows_out, float* scores_out, coot_stream_t stream);
 
+/* ---- join of two galleries: all pairs (left row, right row) at or above a threshold -------------------------------------------------
+ * The tile range search with a prepared gallery on either side.  Pair (i, j), row i of left [N_left, d] and row j of right [N_right, d],
+ * is a hit when left_keep (NULL: no filter) lets row i pass, right_keep row j, left_groups and right_groups are both NULL or
+ * left_groups[i] != right_groups[j] (device int32 [N_left] and [N_right] in one id space, integer compare), and
+ * s(i, j) >= thresholds[i], the IEEE fp32 compare of the range search.  s(i, j) is the fp32 chain of every search here with left row i
+ * as the query: the stored row widened (exact) and left_norms[i] as its norm, which is the norm of the widened row — so the bits are
+ * those of coot_retrieval_range_tile_count / _fill with a float32 copy of left as the queries.  left_dtype and right_dtype are
+ * COOT_GALLERY_* codes and need not agree; left_norms and right_norms are both given (both sides divided by their norms) or both NULL.
+ * The result is the CSR of the range search: the hits of left row i are rows of right, ascending.
+ * A call serves the left rows [row0, row0 + rows), row0 a multiple of 64, rows >= 1, row0 + rows <= N_left, ceil(rows / 64) <= 65535.
+ * thresholds: device fp32 [N_left], indexed by the absolute row.  block_counts: int32 [rows][COOT_RETRIEVAL_RANGE_TABLE_ROW(N_right)],
+ * the table of `rows` queries against a gallery of N_right rows:
+ *   coot_retrieval_cross_join_count writes the first ceil(N_right / 128) entries of every row; a block in which right_keep leaves no
+ *     row is not read, nor is anything for 64 left rows that left_keep masks altogether: their slots are zeros.
+ *   coot_retrieval_range_scan(block_counts, rows, N_right, offsets, counts_out, stream), unchanged.
+ *   coot_retrieval_cross_join_fill: the count call's arguments again, block_base = the scanned table, offsets = int64 [rows], the
+ *     position of the first hit of left row row0 + r at offsets[r] (the scan's, or the scan's shifted by what earlier chunks hold), and
+ *     rows_out / scores_out with room for `capacity` entries: a hit whose position is below capacity is written, the others are not,
+ *     and entries that no hit claims are not touched.  A block in which none of a workgroup's 64 rows has a hit is not read.
+ * No workspace.  No atomic touches global memory: the bytes do not depend on the schedule or on how the left rows are cut into chunks.
+ * A refused call (unknown dtype, a null pointer other than the norms, keeps and groups, one norm or one groups table without the other,
+ * row0 or rows outside their range, N_left, N_right or d < 1, capacity < 0) returns before any launch and writes nothing.  No
+ * allocation, no synchronisation; no pointer is retained. */
+int coot_retrieval_cross_join_count(const void* left, int left_dtype, const float* left_norms, const void* right, int right_dtype,
+                                    const float* right_norms, const uint8_t* left_keep, const uint8_t* right_keep, const int32_t* left_groups,
+                                    const int32_t* right_groups, const float* thresholds, int row0, int rows, int N_left, int N_right, int d,
+                                    int32_t* block_counts, coot_stream_t stream);
+int coot_retrieval_cross_join_fill(const void* left, int left_dtype, const float* left_norms, const void* right, int right_dtype,
+                                   const float* right_norms, const uint8_t* left_keep, const uint8_t* right_keep, const int32_t* left_groups,
+                                   const int32_t* right_groups, const float* thresholds, int row0, int rows, int N_left, int N_right, int d,
+                                   const int32_t* block_base, const int64_t* offsets, int64_t capacity, int32_t* rows_out, float* scores_out,
+                                   coot_stream_t stream);
+
 /* ---- a prepared gallery that changes: rows written in place, their norms with them ---------------------------------------
  * coot_retrieval_rows_put writes the R rows of src [R, d] into the buffer gallery [N, d] and, where norms != NULL, norms[row] of
  * every row it wrote: what a corpus that grows (rows appended into spare capacity) or is re-encoded (rows overwritten) needs,
