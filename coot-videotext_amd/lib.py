@@ -43,6 +43,7 @@ EXPORTS = [
     "coot_retrieval_range_tile_workspace_bytes", "coot_retrieval_range_tile_count", "coot_retrieval_range_tile_fill",
     "coot_retrieval_join_count", "coot_retrieval_join_fill",
     "coot_retrieval_cross_join_count", "coot_retrieval_cross_join_fill",
+    "coot_retrieval_knn_join_workspace_bytes", "coot_retrieval_knn_join",
     "coot_det_shadow_bytes", "coot_det_configure", "coot_det_flush", "coot_event_record", "coot_event_wait", "coot_event_handle", "coot_stream_hop",
     "coot_stream_create_concurrent", "coot_stream_destroy", "coot_streams_overlap",
 ]
@@ -245,6 +246,9 @@ def load():
     lib.coot_retrieval_join_fill.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i64, vp, vp, vp]
     lib.coot_retrieval_cross_join_count.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
     lib.coot_retrieval_cross_join_fill.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i64, vp, vp, vp]
+    lib.coot_retrieval_knn_join_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.coot_retrieval_knn_join_workspace_bytes.restype = C.c_size_t
+    lib.coot_retrieval_knn_join.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, C.c_size_t, vp]
     lib.coot_retrieval_ranks_labeled_workspace_bytes.argtypes = [i32, i32, i32]
     lib.coot_retrieval_ranks_labeled_workspace_bytes.restype = C.c_size_t
     lib.coot_retrieval_ranks_labeled.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]

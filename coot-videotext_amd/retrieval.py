@@ -25,6 +25,8 @@ of rows, the chunks sized by JOIN_TABLE_BYTES (_self_join).
 retrieval_join_device / GalleryIndex.join, count_join: the rows of one index against the rows of another, all pairs at or above the
 left row's threshold, as the same CSR (compute_retrieval_join): coot_retrieval_cross_join_count, _scan, coot_retrieval_cross_join_fill
 per chunk of left rows, under the same budget (_cross_join).
+retrieval_knn_join_device / GalleryIndex.knn_join, knn_graph: the k best partners of EVERY row of an index, in a second index or in
+itself, under the joins' filters (compute_retrieval_knn_join): one call of coot_retrieval_knn_join, both sides read as stored (_knn_join).
 The searches on a prepared gallery share one host check (_check_search) and have one implementation per library call (_topk_few,
 _topk_tile, _topk_grouped, _topk_multi, _topk_scoped), which the public wrapper and the GalleryIndex method both call.
 GalleryIndex.add / update / compact: rows appended or overwritten in place together with their norms (coot_retrieval_rows_put),
@@ -40,7 +42,7 @@ import numpy as np
 from .retrieval_mirror import (VALKEYS, _ahead, _host_offsets, _labeled_metrics, compute_retrieval, compute_retrieval_cosine,  # noqa: F401
                                compute_retrieval_counts_part, compute_retrieval_labeled, compute_retrieval_topk, compute_retrieval_topk_grouped,
                                compute_retrieval_range, compute_retrieval_topk_masked, compute_retrieval_topk_multi, compute_retrieval_topk_scoped,
-                               compute_retrieval_self_join, compute_retrieval_join, strip_bounds)
+                               compute_retrieval_self_join, compute_retrieval_join, compute_retrieval_knn_join, strip_bounds)
 
 
 def _ptr(t):
@@ -746,6 +748,79 @@ def retrieval_join_device(left_gallery, left_norms, right_gallery, right_norms, 
     return _cross_join(left_gallery, left_norms, right_gallery, right_norms, threshold, keep, other_keep, groups, other_groups, max_results)
 
 
+KNN_JOIN_ROWS_MAX = 65535 * 64  # coot_retrieval_knn_join: ceil(N_left / 64) <= 65 535
+
+
+def _knn_join(left, left_norms, right, right_norms, k: int, keep, other_keep, groups, other_groups, exclude_same_row: bool, method=None,
+              own_keep=None, other_own_keep=None):
+    """coot_retrieval_knn_join: one call for any N_left.  Checked in this order: the widths, both norms or none, one device for both
+    sides, groups, keep, k, N_left, then where everything lives.  method, own_keep, other_own_keep: the name and the own filters of
+    GalleryIndex.knn_join / knn_graph."""
+    import torch
+    from . import lib as _lib
+    fn = "retrieval_knn_join_device"
+    who = method or fn
+    assert left.dim() == 2 and right.dim() == 2, (left.shape, right.shape)
+    (nl, d), nr, k = left.shape, right.shape[0], int(k)
+    if right.shape[1] != d:
+        raise ValueError(f"{who}: left rows of width {d}, right rows of width {right.shape[1]}")
+    if (left_norms is None) != (right_norms is None):
+        raise ValueError(f"{who}: one side brings row norms and the other does not (one similarity needs both norms or none)")
+    if right.device != left.device:
+        raise ValueError(f"{who}: the right rows live on {right.device}, the left rows on {left.device}")
+    if (groups is None) != (other_groups is None):
+        raise ValueError(f"{who}: groups and other_groups are given together or not at all (ids of one space, compared by inequality)")
+    if groups is not None:
+        same = other_groups is groups and nr == nl  # (knn_graph: one table, converted once)
+        groups = _check_groups(who, groups, nl, mirror=None)
+        other_groups = groups if same else _check_groups(who, other_groups, nr, mirror=None)
+    if keep is not None:
+        keep = _check_keep(who, keep, nl, mirror=None)
+    if other_keep is not None:
+        other_keep = _check_keep(who, other_keep, nr, mirror=None)
+    if not 1 <= k <= min(nr, 128):
+        raise ValueError(f"{who}: k = {k} is outside 1 .. min(N_right = {nr}, 128)")
+    if not 1 <= nl <= KNN_JOIN_ROWS_MAX:
+        raise ValueError(f"{who}: {nl} left rows; one call takes 1 .. {KNN_JOIN_ROWS_MAX}")
+    _on_device(who, "compute_retrieval_knn_join", left, left_norms, right, right_norms, keep, other_keep, groups, other_groups)
+    dev = left.device
+    for name, t in (("the right norms", right_norms), ("keep", keep), ("other_keep", other_keep), ("groups", groups),
+                    ("other_groups", other_groups), ("the left norms", left_norms)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"{who}: {name} live on {t.device}, the left rows on {dev}")
+    lcode, rcode = _gallery_code(fn, left), _gallery_code(fn, right)
+    for norms, n in ((left_norms, nl), (right_norms, nr)):
+        assert norms is None or (norms.dtype == torch.float32 and tuple(norms.shape) == (n,)), (norms.dtype, norms.shape, n)
+    left, right = left.contiguous(), right.contiguous()
+    if left_norms is not None:
+        left_norms, right_norms = left_norms.contiguous(), right_norms.contiguous()
+    keep, other_keep = _and_own(own_keep, keep), _and_own(other_own_keep, other_keep)
+    lib = _lib.load()
+    ws = torch.empty(lib.coot_retrieval_knn_join_workspace_bytes(nl, nr, k), dtype=torch.uint8, device=dev)
+    idx = torch.empty(nl, k, dtype=torch.int32, device=dev)
+    scores = torch.empty(nl, k, dtype=torch.float32, device=dev)
+    _lib.check(lib.coot_retrieval_knn_join(left.data_ptr(), lcode, _ptr(left_norms), right.data_ptr(), rcode, _ptr(right_norms), _ptr(keep),
+                                           _ptr(other_keep), _ptr(groups), _ptr(other_groups), int(bool(exclude_same_row)), nl, nr, d, k,
+                                           idx.data_ptr(), scores.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "coot_retrieval_knn_join")
+    return idx, scores
+
+
+def retrieval_knn_join_device(left_gallery, left_norms, right_gallery, right_norms, k: int, keep=None, other_keep=None, groups=None,
+                              other_groups=None, exclude_same_row: bool = False):
+    """The k best partners of every left row among the right rows, on galleries as prepared indexes hold them
+    (coot_retrieval_knn_join).  left_gallery [N_left, d], right_gallery [N_right, d]: cuda float32, bfloat16 or float16, each its own;
+    left_norms / right_norms: cuda float32 [N_left] / [N_right] (GalleryIndex.norms), or both None: rows used as they are (one without
+    the other is a ValueError).  keep / other_keep: cuda torch.bool or torch.uint8 [N_left] / [N_right]; groups / other_groups: cuda
+    torch.int32 or torch.int64 [N_left] / [N_right] (int64 is converted once), both or neither.  Pair (i, j) is eligible when keep lets
+    left row i pass, other_keep right row j, the groups are None or groups[i] != other_groups[j], and, with exclude_same_row, j != i
+    (left and right the same rows: a row is not its own neighbour).  Returns (idx int32 [N_left, k], scores float32 [N_left, k]) on the
+    device, nothing synchronises: row i holds the k best eligible right rows, score descending, then the larger row, with the bytes of
+    the similarity the searches rank on with left row i, widened to float32, as the query; fewer than k eligible rows leave a tail of
+    -1 / -inf, and a left row that keep masks is -1 / -inf throughout.  compute_retrieval_knn_join of those similarities, byte for
+    byte.  1 <= k <= min(N_right, 128), whatever the filters hold; N_left <= KNN_JOIN_ROWS_MAX — see GalleryIndex.knn_join."""
+    return _knn_join(left_gallery, left_norms, right_gallery, right_norms, k, keep, other_keep, groups, other_groups, exclude_same_row)
+
+
 # retrieval_topk_multi_device: the table best [M][G] of one library call holds at most this many entries (2^25 x 8 bytes = 256 MiB); a
 # larger search runs as several calls, split where a paragraph ends, over one workspace.  One paragraph is never split: its own table
 # may reach the library's bound.
@@ -1214,8 +1289,8 @@ class GalleryIndex:
         return _self_join(self.gallery, self.norms if self.normalize else None, threshold, keep, groups, None,
                           method="GalleryIndex.count_self_join", own_keep=self.keep, count_only=True)
 
-    def _join(self, who: str, other, threshold, keep, other_keep, groups, other_groups, max_results, count_only: bool):
-        """join / count_join: what two indexes have to share, then _cross_join on what they hold."""
+    def _check_right(self, who: str, other):
+        """What two indexes have to share before rows of one meet rows of the other (join, count_join, knn_join)."""
         if not isinstance(other, GalleryIndex):
             raise TypeError(f"{who}: the right side has to be a GalleryIndex, not {type(other).__name__}")
         if other.gallery.shape[1] != self.gallery.shape[1]:
@@ -1225,6 +1300,10 @@ class GalleryIndex:
                              "(one similarity needs both norms or none)")
         if other.gallery.device != self.gallery.device:
             raise ValueError(f"{who}: this index lives on {self.gallery.device}, the right one on {other.gallery.device}")
+
+    def _join(self, who: str, other, threshold, keep, other_keep, groups, other_groups, max_results, count_only: bool):
+        """join / count_join: what two indexes have to share, then _cross_join on what they hold."""
+        self._check_right(who, other)
         return _cross_join(self.gallery, self.norms if self.normalize else None, other.gallery, other.norms if other.normalize else None,
                            threshold, keep, other_keep, groups, other_groups, max_results, method=who, own_keep=self.keep,
                            other_own_keep=other.keep, count_only=count_only)
@@ -1261,6 +1340,43 @@ class GalleryIndex:
         """How many pairs join would return per left row, int32 [N_left] on the device: the count pass and the scan of every chunk,
         no fill and no synchronisation.  Its sum is the number of pairs."""
         return self._join("GalleryIndex.count_join", right, threshold, keep, other_keep, groups, other_groups, None, True)
+
+    def knn_join(self, right, k: int, keep=None, other_keep=None, groups=None, other_groups=None):
+        """The k best rows of ANOTHER index for EVERY row of this one (the closest training items of every validation item; each
+        clip's hardest negatives in a second split): (idx int32 [N_left, k], scores float32 [N_left, k]) on the device, rows of
+        `right`, best first.  Pair (i, j) is eligible when keep (cuda torch.bool or torch.uint8 [N_left]) and this index's own filter
+        (remove) let row i pass, other_keep ([N_right]) and right's own filter let row j pass, and groups and other_groups are both
+        None or groups[i] != other_groups[j] (cuda torch.int32 or torch.int64 [N_left] and [N_right] in one id space: the source
+        video of a clip; the caller owns the tables, as in search_grouped; exactly one of them is a ValueError).  Row i holds the k
+        best eligible j in the order of every search, score descending, then the larger row; fewer than k eligible rows leave a
+        tail of -1 / -inf, and a row of this index that the left filters mask is -1 / -inf throughout: a removed row does not ask
+        (unlike neighbors).  s(i, j) is, bit for bit, the sim of right.search(self.gallery.float(), 1, want_sim=True), so an
+        unmasked row i is, byte for byte, right.search_scoped(self.gallery[i:i + 1].float(), k, other_groups,
+        exclude=groups[i:i + 1], keep=other_keep), and without groups right.search(self.gallery.float(), k, keep=other_keep):
+        compute_retrieval_knn_join of the similarities, for all nine pairs of storage types.  Both operands are read as their index
+        stores them and both norms are the stored ones: no float32 copy of the left side, no norm pass, and one pass of 64 left rows
+        per workgroup over the right index instead of one sweep per 16 queries.  `right` has to be a GalleryIndex of the same width,
+        the same normalize and on the same device (TypeError / ValueError before anything is launched); right may be this index
+        itself, and then a row returns itself (see knn_graph).  1 <= k <= min(N_right, 128), checked against N_right whatever the
+        filters hold; N_left <= retrieval.KNN_JOIN_ROWS_MAX.  Nothing synchronises."""
+        who = "GalleryIndex.knn_join"
+        self._check_right(who, right)
+        return _knn_join(self.gallery, self.norms if self.normalize else None, right.gallery, right.norms if right.normalize else None, k, keep,
+                         other_keep, groups, other_groups, False, method=who, own_keep=self.keep, other_own_keep=right.keep)
+
+    def knn_graph(self, k: int, keep=None, groups=None):
+        """The k nearest rows of this index for EVERY one of its rows (a k-NN graph for clustering or de-duplication where no
+        threshold is known; hard negatives over a whole split): (idx int32 [N, k], scores float32 [N, k]) on the device.  knn_join
+        of the index with itself, keep (cuda torch.bool or torch.uint8 [N]) applying to both sides as in self_join, and a row never
+        returns itself: with groups=None row j is eligible for row i when j != i, with groups (cuda torch.int32 or torch.int64 [N])
+        when groups[j] != groups[i] — each clip's nearest clips from OTHER videos.  For a row that keep and the index's own filter
+        let pass, the bytes of neighbors([i], k, groups, keep=keep); a row that they mask is -1 / -inf throughout (a removed row does
+        not ask), and an exact duplicate elsewhere in the index is returned.  Against neighbors(arange(N), k): no float32 copy of the
+        gallery and one pass per 64 rows instead of one sweep per 16.  1 <= k <= min(N, 128); nothing synchronises."""
+        who = "GalleryIndex.knn_graph"
+        norms = self.norms if self.normalize else None
+        return _knn_join(self.gallery, norms, self.gallery, norms, k, keep, keep, groups, groups, groups is None, method=who,
+                         own_keep=self.keep, other_own_keep=self.keep)
 
     def neighbors(self, rows, k: int, groups=None, keep=None):
         """More like this: the k best rows for each of the index's own rows, (idx int32 [R, k], scores float32 [R, k]) on the device.

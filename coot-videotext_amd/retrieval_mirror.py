@@ -10,6 +10,7 @@ alike; under a mask per QUERY, the rows with (only) or without (exclude) the id 
 compute_retrieval_range: every column at or above a row's threshold, however many, as CSR.
 compute_retrieval_self_join: the same on a gallery's similarities with itself, read as pairs: the columns right of the diagonal.
 compute_retrieval_join: the same on the similarities of two galleries, with a filter and group ids on either side.
+compute_retrieval_knn_join: the k best partners of every row under those filters, in the order of compute_retrieval_topk.
 compute_retrieval_labeled: ranks and metrics without the assumption "square, ground truth on the diagonal": labels[i] = the gallery
 row of query i; several queries per row, rows without a query and queries without a row (a label outside [0, N)) are allowed.
 strip_bounds / compute_retrieval_counts_part: one strip of rows of the sharded validation; the sum over the strips is the whole."""
@@ -240,6 +241,49 @@ def compute_retrieval_join(sim: np.ndarray, threshold, keep=None, other_keep=Non
         scores.append(s)
         offsets[i + 1] = offsets[i] + len(r)
     return offsets, np.concatenate(rows).astype(np.int32), np.concatenate(scores).astype(sim.dtype)
+
+
+def compute_retrieval_knn_join(sim: np.ndarray, k: int, keep=None, other_keep=None, groups=None, other_groups=None,
+                               exclude_same_row: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+    """The k best partners of every row of a left gallery among the rows of a right one, from their similarities sim [M, N]: (idx
+    int32 [M, k], scores [M, k]).  Pair (i, j) is eligible when keep (bytes or booleans [M], None: every row) lets left row i pass,
+    other_keep ([N]) lets right row j pass, groups and other_groups are both None or groups[i] != other_groups[j] (integers [M] and
+    [N] in one id space; exactly one of them is an error), and, with exclude_same_row, j != i (the self case, sim of a gallery with
+    itself).  Row i holds the k best eligible columns in the order of compute_retrieval_topk, score descending, then column
+    descending; fewer than k eligible columns leave a tail of idx -1, score -inf, and a row that keep masks is -1 / -inf in every
+    slot: it does not ask.  1 <= k <= N whatever the filters hold.  Row i is compute_retrieval_topk_masked(sim[i:i + 1], k,
+    eligible_i); with groups and no other filter it is compute_retrieval_topk_scoped(sim, k, other_groups, exclude=groups)."""
+    sim = np.asarray(sim)
+    assert sim.ndim == 2, sim.shape
+    m, n = sim.shape
+    assert 1 <= k <= n, (sim.shape, k)
+    ask, ok = np.ones(m, bool), np.ones(n, bool)
+    if keep is not None:
+        keep = np.asarray(keep)
+        assert keep.shape == (m,), (keep.shape, m)
+        ask = keep != 0
+    if other_keep is not None:
+        other_keep = np.asarray(other_keep)
+        assert other_keep.shape == (n,), (other_keep.shape, n)
+        ok = other_keep != 0
+    if (groups is None) != (other_groups is None):
+        raise ValueError("compute_retrieval_knn_join: groups and other_groups are given together or not at all")
+    if groups is not None:
+        groups, other_groups = np.asarray(groups), np.asarray(other_groups)
+        assert groups.shape == (m,) and groups.dtype.kind in "iu", (groups.shape, groups.dtype)
+        assert other_groups.shape == (n,) and other_groups.dtype.kind in "iu", (other_groups.shape, other_groups.dtype)
+        groups, other_groups = groups.astype(np.int64), other_groups.astype(np.int64)
+    cols = np.arange(n)
+    idx = np.empty((m, k), np.int32)
+    scores = np.empty((m, k), sim.dtype)
+    for i in range(m):
+        el = ok & ask[i]
+        if groups is not None:
+            el = el & (other_groups != groups[i])
+        if exclude_same_row:
+            el = el & (cols != i)
+        idx[i], scores[i] = compute_retrieval_topk_masked(sim[i:i + 1], k, el)
+    return idx, scores
 
 
 def _host_offsets(fn: str, offsets, m: int, exc=ValueError) -> np.ndarray:

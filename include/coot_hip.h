@@ -652,6 +652,35 @@ int coot_retrieval_cross_join_fill(const void* left, int left_dtype, const float
                                    const int32_t* block_base, const int64_t* offsets, int64_t capacity, int32_t* rows_out, float* scores_out,
                                    coot_stream_t stream);
 
+/* ---- K best partners of every row: a prepared gallery against a second one, or against itself ------------------------------------
+ * For every row i of left [N_left, d] the K best rows j of right [N_right, d], without a float32 copy of the left side, without a norm
+ * pass and in one call for any N_left.  Pair (i, j) is eligible when left_keep (NULL: no filter) lets row i pass, right_keep row j,
+ * left_groups and right_groups are both NULL or left_groups[i] != right_groups[j] (device int32 [N_left] and [N_right] in one id space,
+ * integer compare), and, with exclude_same_row = 1, j != i (the self case: left and right the same gallery).  Row i of idx_out /
+ * score_out (int32 / fp32 [N_left][K]) holds the K best eligible j by the order of every search here, score descending, then the
+ * larger row; fewer than K eligible rows leave a tail of idx -1, score -inf, and a left row that left_keep masks is -1 / -inf in all K
+ * slots: it does not ask.  s(i, j) is the fp32 chain of every search with left row i as the query: the stored row widened (exact) and
+ * left_norms[i] as its norm — bit for bit the sim_out of coot_retrieval_topk_index with a float32 copy of left as the queries.  So an
+ * unmasked row is, byte for byte, the row coot_retrieval_topk_scoped returns for that query with exclude = 1 and scope = left_groups[i],
+ * and without groups and exclude_same_row the row of coot_retrieval_topk_index under keep = right_keep.
+ * left_dtype and right_dtype are COOT_GALLERY_* codes and need not agree; left_norms and right_norms are both given (both sides divided
+ * by their norms) or both NULL.  1 <= K <= min(N_right, 128), checked against N_right whatever the filters hold; ceil(N_left / 64) <=
+ * 65535.  A workgroup serves 64 left rows and a share of the 128-row blocks of right; a block in which right_keep leaves no row is not
+ * read, nor is anything for 64 left rows that left_keep masks altogether.  The right gallery is cut into S shares whose lists are merged
+ * by rank (automatic: enough workgroups to fill the device; coot_set_option("rt_knn_splits", n) fixes S for tests, 0 = automatic); the
+ * result depends on neither S, the schedule nor the other rows of the call.  No atomic touches global memory.
+ * workspace (16-byte aligned): coot_retrieval_knn_join_workspace_bytes(N_left, N_right, K), the lists of the shares under the split
+ * option in force when it is asked; it needs no device and is 256 for arguments out of range.  Reads left, right, the norms, keeps and
+ * groups; writes idx_out, score_out and the workspace.  A refused call (unknown dtype, a null pointer other than the norms, keeps and
+ * groups, one norm or one groups table without the other, exclude_same_row not 0 or 1, N_left, N_right, d or K outside their range,
+ * workspace misaligned or too small) returns before any launch and writes nothing.  No allocation, no synchronisation; no pointer is
+ * retained. */
+size_t coot_retrieval_knn_join_workspace_bytes(int N_left, int N_right, int K);
+int coot_retrieval_knn_join(const void* left, int left_dtype, const float* left_norms, const void* right, int right_dtype,
+                            const float* right_norms, const uint8_t* left_keep, const uint8_t* right_keep, const int32_t* left_groups,
+                            const int32_t* right_groups, int exclude_same_row, int N_left, int N_right, int d, int K, int32_t* idx_out,
+                            float* score_out, void* workspace, size_t workspace_bytes, coot_stream_t stream);
+
 /* ---- a prepared gallery that changes: rows written in place, their norms with them ---------------------------------------
  * coot_retrieval_rows_put writes the R rows of src [R, d] into the buffer gallery [N, d] and, where norms != NULL, norms[row] of
  * every row it wrote: what a corpus that grows (rows appended into spare capacity) or is re-encoded (rows overwritten) needs,
