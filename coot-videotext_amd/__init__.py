@@ -15,6 +15,7 @@ from .nets import TransformerHip, pack_by_count  # noqa: F401
 from .retrieval import (RETRIEVAL_FEW_MAX, GalleryIndex, compute_retrieval, compute_retrieval_cosine, compute_retrieval_counts_part,  # noqa: F401
                         compute_retrieval_labeled, compute_retrieval_labeled_device, compute_retrieval_range, compute_retrieval_topk,
                         compute_retrieval_topk_grouped, compute_retrieval_self_join, retrieval_self_join_device,
+                        compute_retrieval_components, retrieval_components_device,
                         compute_retrieval_join, retrieval_join_device, compute_retrieval_knn_join, retrieval_knn_join_device,
                         compute_retrieval_topk_masked, compute_retrieval_topk_multi, compute_retrieval_topk_scoped, retrieval_metrics_device,
                         retrieval_range_device, retrieval_ranks_labeled_device, retrieval_ranks_part_device, retrieval_topk_device, retrieval_topk_grouped_device,

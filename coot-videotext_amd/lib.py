@@ -44,6 +44,7 @@ EXPORTS = [
     "coot_retrieval_join_count", "coot_retrieval_join_fill",
     "coot_retrieval_cross_join_count", "coot_retrieval_cross_join_fill",
     "coot_retrieval_knn_join_workspace_bytes", "coot_retrieval_knn_join",
+    "coot_retrieval_components",
     "coot_det_shadow_bytes", "coot_det_configure", "coot_det_flush", "coot_event_record", "coot_event_wait", "coot_event_handle", "coot_stream_hop",
     "coot_stream_create_concurrent", "coot_stream_destroy", "coot_streams_overlap",
 ]
@@ -249,6 +250,7 @@ def load():
     lib.coot_retrieval_knn_join_workspace_bytes.argtypes = [i32, i32, i32]
     lib.coot_retrieval_knn_join_workspace_bytes.restype = C.c_size_t
     lib.coot_retrieval_knn_join.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, C.c_size_t, vp]
+    lib.coot_retrieval_components.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp]
     lib.coot_retrieval_ranks_labeled_workspace_bytes.argtypes = [i32, i32, i32]
     lib.coot_retrieval_ranks_labeled_workspace_bytes.restype = C.c_size_t
     lib.coot_retrieval_ranks_labeled.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]

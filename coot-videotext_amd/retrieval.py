@@ -22,6 +22,8 @@ coot_retrieval_range_tile_count, _scan, _tile_fill from there on, one call per p
 retrieval_self_join_device / GalleryIndex.self_join, count_self_join: the gallery against itself, all pairs (i, j), i < j, at or above
 row i's threshold, as the same CSR (compute_retrieval_self_join): coot_retrieval_join_count, _scan, coot_retrieval_join_fill per chunk
 of rows, the chunks sized by JOIN_TABLE_BYTES (_self_join).
+retrieval_components_device / GalleryIndex.components, deduplicate: the connected components of those pairs, a cluster label per row
+(compute_retrieval_components): one call of coot_retrieval_components, one sweep of the upper triangle, no pair list (_components).
 retrieval_join_device / GalleryIndex.join, count_join: the rows of one index against the rows of another, all pairs at or above the
 left row's threshold, as the same CSR (compute_retrieval_join): coot_retrieval_cross_join_count, _scan, coot_retrieval_cross_join_fill
 per chunk of left rows, under the same budget (_cross_join).
@@ -42,7 +44,8 @@ import numpy as np
 from .retrieval_mirror import (VALKEYS, _ahead, _host_offsets, _labeled_metrics, compute_retrieval, compute_retrieval_cosine,  # noqa: F401
                                compute_retrieval_counts_part, compute_retrieval_labeled, compute_retrieval_topk, compute_retrieval_topk_grouped,
                                compute_retrieval_range, compute_retrieval_topk_masked, compute_retrieval_topk_multi, compute_retrieval_topk_scoped,
-                               compute_retrieval_self_join, compute_retrieval_join, compute_retrieval_knn_join, strip_bounds)
+                               compute_retrieval_self_join, compute_retrieval_components, compute_retrieval_join, compute_retrieval_knn_join,
+                               strip_bounds)
 
 
 def _ptr(t):
@@ -630,6 +633,52 @@ def retrieval_self_join_device(gallery, norms, threshold, keep=None, groups=None
     return _self_join(gallery, norms, threshold, keep, groups, max_results)
 
 
+COMPONENTS_ROWS_MAX = 65535 * 64  # coot_retrieval_components: one launch covers all rows, ceil(N / 64) <= 65 535
+
+
+def _components(gallery, norms, threshold, keep, groups, method=None, own_keep=None):
+    """One call of coot_retrieval_components.  Checked in this order: the number of rows, then as _self_join: groups, keep, the
+    threshold's type and shape, then where everything lives.  method, own_keep: the name and the own filter of
+    GalleryIndex.components / deduplicate."""
+    import torch
+    from . import lib as _lib
+    fn = "retrieval_components_device"
+    who = method or fn
+    assert gallery.dim() == 2, gallery.shape
+    n, d = gallery.shape
+    if n > COMPONENTS_ROWS_MAX:
+        raise ValueError(f"{who}: a gallery of {n} rows; one launch covers all rows, at most {COMPONENTS_ROWS_MAX} (ceil(N / 64) <= 65535)")
+    if groups is not None:
+        groups = _check_groups(who, groups, n, mirror=None)
+    if keep is not None:
+        keep = _check_keep(who, keep, n, mirror=None)
+    thr = _check_threshold(who, threshold, n)
+    _on_device(who, "compute_retrieval_components", gallery, norms, keep, groups)
+    code = _gallery_code(fn, gallery)
+    assert norms is None or (norms.dtype == torch.float32 and tuple(norms.shape) == (n,)), (norms.dtype, norms.shape, n)
+    gallery, norms, dev = gallery.contiguous(), None if norms is None else norms.contiguous(), gallery.device
+    if isinstance(thr, np.ndarray):
+        thr = torch.from_numpy(thr).to(dev)
+    elif thr.device != dev:
+        raise ValueError(f"{who}: threshold lives on {thr.device}, the gallery on {dev}")
+    thr = thr.contiguous()
+    keep = _and_own(own_keep, keep)
+    parent = torch.empty(n, dtype=torch.int32, device=dev)
+    labels = torch.empty(n, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().coot_retrieval_components(gallery.data_ptr(), code, _ptr(norms), _ptr(keep), _ptr(groups), thr.data_ptr(), n, d,
+                                                     parent.data_ptr(), labels.data_ptr(), _stream()), "coot_retrieval_components")
+    return labels
+
+
+def retrieval_components_device(gallery, norms, threshold, keep=None, groups=None):
+    """The connected components of a gallery, as a prepared index holds it, under the pairs of retrieval_self_join_device with the
+    same arguments (coot_retrieval_components): labels int32 [N] on the device, no synchronisation.  gallery cuda float32, bfloat16 or
+    float16 [N, d], N <= COMPONENTS_ROWS_MAX, norms cuda float32 [N] (GalleryIndex.norms) or None: rows used as they are; threshold,
+    keep and groups as in retrieval_self_join_device.  labels[i] is the smallest row of row i's component, i itself without an edge,
+    -1 where keep masks the row — see GalleryIndex.components."""
+    return _components(gallery, norms, threshold, keep, groups)
+
+
 _CROSS_JOIN_TILE = 64  # coot_retrieval_cross_join_count: the row tile; a chunk of left rows starts at a multiple of it
 _CROSS_JOIN_ROWS_MAX = 65535 * _CROSS_JOIN_TILE  # ceil(rows / 64) <= 65 535
 
@@ -964,7 +1013,8 @@ class GalleryIndex:
     Range search.  search_range(queries, threshold) returns every row at or above a query's threshold, however many, as CSR (offsets,
     rows, scores), and count_range their number: see the methods.  keep and the index's own filter apply as in search.
     self_join(threshold) is the same question about the gallery itself: all pairs of rows at or above a threshold, each once;
-    count_self_join their number per row.  join(right, threshold) asks it about two indexes: all pairs (row of this index, row of
+    count_self_join their number per row; components(threshold) the clusters those pairs form, a label per row, and
+    deduplicate(threshold) withdraws all but the smallest row of every cluster.  join(right, threshold) asks it about two indexes: all pairs (row of this index, row of
     right) at or above a threshold, with a filter and group ids on either side; count_join their number per left row.
 
     Growth.  index.n (= len(index)) rows are searched, index.capacity rows fit the buffer; index.gallery, index.norms and index.keep
@@ -1288,6 +1338,39 @@ class GalleryIndex:
         fill and no synchronisation.  Its sum is the number of pairs."""
         return _self_join(self.gallery, self.norms if self.normalize else None, threshold, keep, groups, None,
                           method="GalleryIndex.count_self_join", own_keep=self.keep, count_only=True)
+
+    def components(self, threshold, keep=None, groups=None):
+        """DUPLICATE CLUSTERS: the connected components of the gallery under the pairs of self_join(threshold, keep=keep,
+        groups=groups), as a label per row, int32 [N] on the device; nothing synchronises.  The edge set is exactly that hit set:
+        pair (i, j), i < j, is an edge when keep and the index's own filter (remove) let BOTH rows pass, groups is None or groups[i] !=
+        groups[j], and s(i, j) >= threshold[i] in float32, with the bits of s of every search; threshold takes self_join's three forms
+        (a Python number, N numbers on the host, a cuda torch.float32 tensor [N]), and NaN, -0 and the infinities follow from the
+        same compare.  labels[i] is the smallest row number in the connected component of row i: a row without an edge labels itself; a
+        row that the filters mask is -1, and is no vertex, so it does not connect its neighbours.  With groups, two rows of one group
+        are never joined directly; they may still land in one component through a row of another group.  The rows to keep when a
+        split is frozen are those with labels[i] == i (see deduplicate).
+        compute_retrieval_components of the similarities, byte for byte: the result is a function of the edge set only and depends on
+        neither the schedule, the storage type (beyond the exact widening) nor a rerun.  One call of coot_retrieval_components: the
+        upper triangle is swept once, as count_self_join sweeps it, and each hit is a union in a parent array of N int32 — no table,
+        no scan, no fill pass, no pair list, no chunks; 8 bytes per row beyond the index (the workspace and the labels).  N <=
+        retrieval.COMPONENTS_ROWS_MAX (ValueError), because one launch covers all rows."""
+        return _components(self.gallery, self.norms if self.normalize else None, threshold, keep, groups,
+                           method="GalleryIndex.components", own_keep=self.keep)
+
+    def deduplicate(self, threshold, keep=None, groups=None):
+        """components(threshold, keep=keep, groups=groups), and every row that is not the smallest of its cluster withdrawn, as
+        remove() withdraws it: the rows with labels[i] >= 0 and labels[i] != i leave index.keep, on the device, without a
+        synchronisation and without compact().  Returns labels.  Each cluster keeps its smallest row; masked rows (-1) are left as
+        they were.  Afterwards count_self_join(threshold, keep=keep, groups=groups).sum() is 0: two surviving rows with an edge would
+        have shared a component.  restore() brings every row back."""
+        import torch
+        labels = _components(self.gallery, self.norms if self.normalize else None, threshold, keep, groups,
+                             method="GalleryIndex.deduplicate", own_keep=self.keep)
+        n, dev = self.gallery.shape[0], self.gallery.device
+        if self.keep is None:
+            self.keep = torch.ones(n, dtype=torch.bool, device=dev)
+        self.keep &= ~((labels >= 0) & (labels != torch.arange(n, dtype=torch.int32, device=dev)))
+        return labels
 
     def _check_right(self, who: str, other):
         """What two indexes have to share before rows of one meet rows of the other (join, count_join, knn_join)."""

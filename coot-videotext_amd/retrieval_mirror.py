@@ -9,6 +9,7 @@ best row; the K best groups for a PARAGRAPH of queries (MaxSim), whose offsets _
 alike; under a mask per QUERY, the rows with (only) or without (exclude) the id the query brings.
 compute_retrieval_range: every column at or above a row's threshold, however many, as CSR.
 compute_retrieval_self_join: the same on a gallery's similarities with itself, read as pairs: the columns right of the diagonal.
+compute_retrieval_components: the connected components of those pairs, a cluster label per row: a plain host union-find.
 compute_retrieval_join: the same on the similarities of two galleries, with a filter and group ids on either side.
 compute_retrieval_knn_join: the k best partners of every row under those filters, in the order of compute_retrieval_topk.
 compute_retrieval_labeled: ranks and metrics without the assumption "square, ground truth on the diagonal": labels[i] = the gallery
@@ -196,6 +197,35 @@ def compute_retrieval_self_join(sim: np.ndarray, threshold, keep=None, groups=No
         scores.append(s)
         offsets[i + 1] = offsets[i] + len(r)
     return offsets, np.concatenate(rows).astype(np.int32), np.concatenate(scores).astype(sim.dtype)
+
+
+def compute_retrieval_components(sim: np.ndarray, threshold, keep=None, groups=None) -> np.ndarray:
+    """The connected components of a gallery under the pairs of compute_retrieval_self_join(sim, threshold, keep, groups), from its
+    similarities with itself, sim [N, N]: labels int32 [N].  Pair (i, j), i < j, is an edge when keep lets BOTH rows pass, groups is
+    None or groups[i] != groups[j], and sim[i, j] >= threshold[i], the IEEE compare (a NaN on either side is no edge, -0 >= +0 holds,
+    -inf joins every kept pair that is not a NaN).  labels[i] is the smallest row number in row i's component; a row without an edge
+    labels itself; a row that keep masks is -1 and is no vertex, so it does not connect its neighbours.  With groups two rows of one
+    group are never joined directly, but may land in one component through a row of another group.  A plain host union-find over
+    the hit definition: each root is linked below the smaller root, so a root is its set's smallest member."""
+    offsets, rows, _ = compute_retrieval_self_join(sim, threshold, keep=keep, groups=groups)
+    n = len(offsets) - 1
+    parent = np.arange(n)
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    for i in range(n):
+        for j in rows[offsets[i]:offsets[i + 1]]:
+            a, b = find(i), find(int(j))
+            if a != b:
+                parent[max(a, b)] = min(a, b)
+    labels = np.array([find(i) for i in range(n)], np.int32).reshape(n)
+    if keep is not None:
+        labels[np.asarray(keep) == 0] = -1
+    return labels
 
 
 def compute_retrieval_join(sim: np.ndarray, threshold, keep=None, other_keep=None, groups=None,

@@ -681,6 +681,28 @@ int coot_retrieval_knn_join(const void* left, int left_dtype, const float* left_
                             const int32_t* right_groups, int exclude_same_row, int N_left, int N_right, int d, int K, int32_t* idx_out,
                             float* score_out, void* workspace, size_t workspace_bytes, coot_stream_t stream);
 
+/* ---- connected components of the self-join: a cluster label per gallery row, in one sweep -------------------------------------------
+ * The edge set is the hit set of coot_retrieval_join_count / _fill over the whole gallery: pair (i, j), i < j, is an edge when keep
+ * (NULL: no filter) lets BOTH rows pass, groups is NULL or groups[i] != groups[j] (device int32 [N], integer compare), and
+ * s(i, j) >= thresholds[i] (device fp32 [N]), the IEEE fp32 compare and the bits of s of the self-join.  labels[i] (int32 [N]) is the
+ * smallest row number in the connected component of row i under those edges: a row without an edge labels itself, a row that keep
+ * masks is -1 and is no vertex, so it does not connect its neighbours.  With groups two rows of one group are never joined directly but
+ * may share a component through a row of another group.
+ * Three launches on the stream: parent[i] = i; the count pass of the self-join over the whole upper triangle (one grid: ceil(N / 64) <=
+ * 65535 row tiles; blocks left of the diagonal and blocks in which keep leaves no row are not read), in which every hit is a union in
+ * parent instead of a count; labels from parent.  No table, no scan, no fill pass, no pair list: parent (int32 [N], a workspace whose
+ * contents before and after the call mean nothing) and labels are all the memory there is.
+ * The union-find keeps parent[x] <= x and only ever lowers a value (a root is linked below a smaller root by compare-and-swap, paths
+ * are halved by atomic minimum), every loop strictly descends and none waits for another workgroup; the root of a set is its smallest
+ * member, so labels is a function of the edge set alone: it depends on neither the schedule, the grid, the storage type nor a rerun.
+ * coot_set_option("rt_comp_blocks_per_wg", n) fixes how many 128-row blocks a workgroup walks (tests; 0 = automatic: one, up to 2^20
+ * workgroups).  Integer atomics on parent only; no floating-point atomic.
+ * Reads gallery, gallery_norms (NULL: rows used as they are), keep, groups and thresholds; writes parent and labels.  A refused call
+ * (unknown dtype, a null pointer other than gallery_norms, keep and groups, N or d < 1, ceil(N / 64) > 65535) returns before any launch
+ * and writes nothing.  No allocation, no synchronisation; no pointer is retained. */
+int coot_retrieval_components(const void* gallery, int gallery_dtype, const float* gallery_norms, const uint8_t* keep, const int32_t* groups,
+                              const float* thresholds, int N, int d, int32_t* parent, int32_t* labels, coot_stream_t stream);
+
 /* ---- a prepared gallery that changes: rows written in place, their norms with them ---------------------------------------
  * coot_retrieval_rows_put writes the R rows of src [R, d] into the buffer gallery [N, d] and, where norms != NULL, norms[row] of
  * every row it wrote: what a corpus that grows (rows appended into spare capacity) or is re-encoded (rows overwritten) needs,
