@@ -321,18 +321,7 @@ static void layout_scratch(const coot_net_config& c, int N, long Ttok, Arena& A,
 }
 
 static thread_local const unsigned long long* g_seed_dev = nullptr;  // device base seed of the current call
-static DropCfg mkdrop(int train, float p, uint64_t seed, unsigned site) {
-  DropCfg d;
-  if (train && p > 0.f) {
-    double t = (double)p * 4294967296.0;
-    d.thr = t >= 4294967295.0 ? 4294967295u : (unsigned)t;
-    if (d.thr == 0) d.thr = 1;
-    if (d.thr < 65536u) d.thr = 65536u;  // 16-bit compare (common.h): p quantised to 1/65536, inv_keep from the quantised value
-    d.inv_keep = (float)(1.0 / (1.0 - (double)(d.thr >> 16) / 65536.0));
-    d.seed = seed; d.site = site; d.seed_ptr = g_seed_dev;
-  }
-  return d;
-}
+static DropCfg mkdrop(int train, float p, uint64_t seed, unsigned site) { return make_drop(train, p, seed, site, g_seed_dev); }  // rowops.h
 static void epi_drop(GemmEpi& e, const DropCfg& d, long ld) {
   e.drop_thr = d.thr; e.drop_inv_keep = d.inv_keep; e.drop_seed = d.seed; e.drop_seed_ptr = d.seed_ptr; e.drop_site = d.site; e.drop_ld = ld;
 }
@@ -372,12 +361,12 @@ static int attention_all(AttnArgs a, const Segs& sg, bool cross, bool bwd, hipSt
   if (sg.cu) {  // packed rows: the short kernels, every sequence at its own row offset (both segments in one launch)
     COOT_REQUIRE(attn_short_path(sg.L[0]) && (sg.n == 1 || attn_short_path(sg.L[1])), "packed rows need the short attention kernels (L <= 128)");
     a.cu = sg.cu; a.lens = sg.lens[0]; a.Nseq = sg.N[0]; a.Lq = sg.L[0]; a.Lk = sg.L[0];
-    if (sg.n == 2) { a.Nseq2 = sg.N[1]; a.L2 = sg.L[1]; a.lens2 = sg.lens[1]; a.seed2_delta = 0x9E3779B97F4A7C15ull; }
+    if (sg.n == 2) { a.Nseq2 = sg.N[1]; a.L2 = sg.L[1]; a.lens2 = sg.lens[1]; a.seed2_delta = kAttnSeed2Delta; }
     return bwd ? launch_attn_bwd(a, st) : launch_attn_fwd(a, st);
   }
   if (sg.n == 2 && attn_short_path(sg.L[0]) && attn_short_path(sg.L[1])) {  // both segments in ONE launch of the short kernels
     a.lens = sg.lens[0]; a.Nseq = sg.N[0]; a.Lq = sg.L[0]; a.Lk = sg.L[0];
-    a.Nseq2 = sg.N[1]; a.L2 = sg.L[1]; a.lens2 = sg.lens[1]; a.seed2_delta = 0x9E3779B97F4A7C15ull;
+    a.Nseq2 = sg.N[1]; a.L2 = sg.L[1]; a.lens2 = sg.lens[1]; a.seed2_delta = kAttnSeed2Delta;
     return bwd ? launch_attn_bwd(a, st) : launch_attn_fwd(a, st);
   }
   long row = 0;
@@ -391,7 +380,7 @@ static int attention_all(AttnArgs a, const Segs& sg, bool cross, bool bwd, hipSt
       a.dq = base.dq + row * base.lddq; a.dk = base.dk + row * base.lddk; a.dv = base.dv + row * base.lddv;
     }
     a.lens = sg.lens[s]; a.Nseq = sg.N[s]; a.Lq = sg.L[s]; a.Lk = sg.L[s];
-    a.drop.seed = base.drop.seed + (unsigned long long)s * 0x9E3779B97F4A7C15ull;
+    a.drop.seed = base.drop.seed + (unsigned long long)s * kAttnSeed2Delta;
     RUN(bwd ? launch_attn_bwd(a, st) : launch_attn_fwd(a, st));
     row += (long)sg.N[s] * sg.L[s];
   }
@@ -455,7 +444,7 @@ static int layer_fwd(const coot_net_config& c, const float* P, const LayerP& lp,
     if (attn_in_chain) {
       f.attn.on = 1; f.attn.qkv = b.q; f.attn.lse = b.lse; f.ctx_w = b.ctx; f.attn.drop = a.drop; f.attn.scale = a.scale;
       f.attn.N0 = sg.N[0]; f.attn.L0 = sg.L[0]; f.attn.lens0 = sg.lens[0];
-      if (sg.n > 1) { f.attn.N1 = sg.N[1]; f.attn.L1 = sg.L[1]; f.attn.lens1 = sg.lens[1]; f.attn.seed2_delta = 0x9E3779B97F4A7C15ull; }
+      if (sg.n > 1) { f.attn.N1 = sg.N[1]; f.attn.L1 = sg.L[1]; f.attn.lens1 = sg.lens[1]; f.attn.seed2_delta = kAttnSeed2Delta; }
     }
     f.bo = P + lp.bo; f.ln1g = P + lp.ln1g; f.ln1b = P + lp.ln1b; f.b1 = P + lp.b1; f.b2 = P + lp.b2; f.ln2g = P + lp.ln2g; f.ln2b = P + lp.ln2b;
     f.r1 = b.r1; f.z1 = b.z1; f.h1 = b.h1; f.a1 = b.a1; f.r2 = b.r2; f.z2 = b.z2; f.z2_f32 = z2_f32; f.ldz2_f32 = ldz2_f32;

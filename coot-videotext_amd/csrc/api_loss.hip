@@ -183,6 +183,38 @@ int coot_debug_gemm_nt(const coot_gemm_nt_args* a, coot_stream_t stream) {
   if (a->part_ws) set_partials_workspace(nullptr, 0);
   return rc;
 }
+// tests: the attention descriptor as attention_all (api.hip) fills it, dropout by the networks' own make_drop (rowops.h)
+int coot_debug_attn(const coot_attn_args* a, int backward, coot_stream_t stream) {
+  COOT_REQUIRE(a, "debug_attn: null arguments");
+  COOT_REQUIRE(a->q && a->k && a->v && a->o && a->lse && a->lens, "debug_attn: null pointer");
+  COOT_REQUIRE(a->Nseq >= 1 && a->Lq >= 1 && a->Lk >= 1 && a->H >= 1, "debug_attn: Nseq, Lq, Lk, H must be positive");
+  COOT_REQUIRE(a->dh == 16 || a->dh == 32 || a->dh == 48 || a->dh == 64, "debug_attn: d_head=%d unsupported (16,32,48,64)", a->dh);
+  const int64_t D = (int64_t)a->H * a->dh;
+  COOT_REQUIRE(a->ldq % 8 == 0 && a->ldk % 8 == 0 && a->ldv % 8 == 0 && a->ldo % 8 == 0 && a->ldq >= D && a->ldk >= D && a->ldv >= D && a->ldo >= D,
+               "debug_attn: strides must be multiples of 8 and at least H * dh");
+  COOT_REQUIRE(a->Nseq2 >= 0 && a->p >= 0.f && a->p < 1.f, "debug_attn: Nseq2 >= 0, 0 <= p < 1");
+  if (a->Nseq2 > 0 || a->cu) {  // a second segment and packed rows exist in the short kernels only (attention_all splits or refuses the rest)
+    COOT_REQUIRE(a->Lq == a->Lk && attn_short_path(a->Lk), "debug_attn: a second segment / packed rows need self-attention on the short kernels");
+    COOT_REQUIRE(a->Nseq2 == 0 || (a->lens2 && attn_short_path(a->L2)), "debug_attn: the second segment needs lens2 and a short L2");
+  }
+  if (backward) {
+    COOT_REQUIRE(a->dout && a->delta && a->dq && a->dk && a->dv, "debug_attn: backward: null pointer");
+    COOT_REQUIRE(a->lddo % 8 == 0 && a->lddq % 8 == 0 && a->lddk % 8 == 0 && a->lddv % 8 == 0 && a->lddo >= D && a->lddq >= D && a->lddk >= D && a->lddv >= D,
+                 "debug_attn: backward: strides must be multiples of 8 and at least H * dh");
+  }
+  AttnArgs g;
+  g.q = (const bf16_t*)a->q; g.ldq = a->ldq; g.k = (const bf16_t*)a->k; g.ldk = a->ldk; g.v = (const bf16_t*)a->v; g.ldv = a->ldv;
+  g.o = (bf16_t*)a->o; g.ldo = a->ldo; g.lse = a->lse; g.lens = (const long long*)a->lens;
+  g.Nseq = a->Nseq; g.Lq = a->Lq; g.Lk = a->Lk; g.H = a->H; g.dh = a->dh; g.scale = 1.0f / sqrtf((float)a->dh);
+  if (a->Nseq2 > 0) { g.Nseq2 = a->Nseq2; g.L2 = a->L2; g.lens2 = (const long long*)a->lens2; g.seed2_delta = kAttnSeed2Delta; }
+  g.cu = a->cu;
+  g.drop = make_drop(1, a->p, a->seed, a->site, nullptr);
+  if (backward) {
+    g.dout = (const bf16_t*)a->dout; g.lddo = a->lddo; g.delta = a->delta;
+    g.dq = (bf16_t*)a->dq; g.lddq = a->lddq; g.dk = (bf16_t*)a->dk; g.lddk = a->lddk; g.dv = (bf16_t*)a->dv; g.lddv = a->lddv;
+  }
+  return backward ? launch_attn_bwd(g, (hipStream_t)stream) : launch_attn_fwd(g, (hipStream_t)stream);
+}
 size_t coot_gemm_tn_workspace_bytes(int T, int Mo, int No) { return gemm_tn_workspace_floats(T, Mo, No, 1) * sizeof(float); }
 int coot_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, int T, int Mo, int No, float* C, int64_t ldc,
                  void* workspace, size_t workspace_bytes, coot_stream_t stream) {

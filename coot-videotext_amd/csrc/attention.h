@@ -32,6 +32,9 @@ struct AttnArgs {
   bf16_t* dv = nullptr; long lddv = 0;
 };
 
+// what every caller adds to the dropout seed for the second segment (AttnArgs::seed2_delta, or drop.seed of a second launch)
+constexpr unsigned long long kAttnSeed2Delta = 0x9E3779B97F4A7C15ull;
+
 int launch_attn_fwd(const AttnArgs& a, hipStream_t stream);
 int launch_attn_bwd(const AttnArgs& a, hipStream_t stream);
 // 1 (default): self-attention with L <= 128 uses the one-workgroup-per-(sequence, head) kernels; 0: chunked kernels (A/B switch)

@@ -8,6 +8,20 @@ struct DropCfg {
   unsigned thr = 0; float inv_keep = 1.0f; unsigned long long seed = 0; unsigned site = 0;
   const unsigned long long* seed_ptr = nullptr;  // device base seed added to `seed`
 };
+// dropout probability -> threshold and keep-scale (the one place that quantises p: the networks' mkdrop in api.hip, the host mask
+// generators coot_debug_*_dropout_scales and coot_debug_attn all go through it)
+inline DropCfg make_drop(int train, float p, unsigned long long seed, unsigned site, const unsigned long long* seed_ptr) {
+  DropCfg d;
+  if (train && p > 0.f) {
+    double t = (double)p * 4294967296.0;
+    d.thr = t >= 4294967295.0 ? 4294967295u : (unsigned)t;
+    if (d.thr == 0) d.thr = 1;
+    if (d.thr < 65536u) d.thr = 65536u;  // 16-bit compare (common.h): p quantised to 1/65536, inv_keep from the quantised value
+    d.inv_keep = (float)(1.0 / (1.0 - (double)(d.thr >> 16) / 65536.0));
+    d.seed = seed; d.site = site; d.seed_ptr = seed_ptr;
+  }
+  return d;
+}
 
 struct LnFwd {
   const void* x = nullptr; int x_f32 = 1; long ldx = 0;  // [R, D]

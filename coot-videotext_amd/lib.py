@@ -27,7 +27,7 @@ EXPORTS = [
     "coot_net_param_info", "coot_net_out_dim", "coot_net_wpack_bytes", "coot_net_pack_weights", "coot_nets_pack_weights",
     "coot_net_saved_bytes", "coot_net_scratch_bytes", "coot_net_fwd", "coot_net_bwd", "coot_net_grads_overwrite", "coot_nets_zero_grads", "coot_nets_zero_grads_ex", "coot_debug_written_matrices", "coot_pack_fwd",
     "coot_pack_bwd", "coot_contrastive_scratch_bytes", "coot_contrastive_fwd_bwd", "coot_contrastive_fwd_bwd_part", "coot_contrastive_f32_scratch_bytes", "coot_contrastive_fwd_bwd_f32", "coot_cyclecons_fwd_bwd",
-    "coot_gemm_nt", "coot_debug_gemm_nt", "coot_gemm_tn", "coot_gemm_tn_batch", "coot_debug_tn_xcd_map", "coot_debug_clock_monitor", "coot_gemm_tn_workspace_bytes", "coot_ln_fwd", "coot_attn_fwd", "coot_probe_tr16", "coot_timing_enable",
+    "coot_gemm_nt", "coot_debug_gemm_nt", "coot_gemm_tn", "coot_gemm_tn_batch", "coot_debug_tn_xcd_map", "coot_debug_clock_monitor", "coot_gemm_tn_workspace_bytes", "coot_ln_fwd", "coot_attn_fwd", "coot_debug_attn", "coot_probe_tr16", "coot_timing_enable",
     "coot_timing_collect", "coot_step_workspace_bytes", "coot_train_step", "coot_step_forward", "coot_step_backward",
     "coot_adam_step", "coot_radam_step", "coot_step_update", "coot_step_set_global_done_events", "coot_step_device_state_bytes", "coot_step_set_device_state", "coot_step_loss_scaler_bytes", "coot_step_set_loss_scaler", "coot_step_unscale_grads", "coot_step_grad_clip_bytes", "coot_step_set_grad_clip", "coot_step_grad_norm", "coot_collate_level", "coot_collate_packed", "coot_sample_cycle_indices", "coot_step_set_cycle_indices", "coot_step_input_stage_bytes", "coot_step_set_input_stages", "coot_step_set_next_batch", "coot_contrastive_fwd_bwd_dp", "coot_contrastive_fwd_bwd_dp_blocks", "coot_retrieval_workspace_bytes", "coot_retrieval_ranks", "coot_retrieval_topk_workspace_bytes", "coot_retrieval_topk",
     "coot_retrieval_ranks_part_workspace_bytes", "coot_retrieval_ranks_part", "coot_retrieval_metrics",
@@ -101,6 +101,17 @@ class GemmNtArgs(C.Structure):
                 ("res", C.c_void_p), ("ldres", C.c_int64), ("pe", C.c_void_p), ("pe_L", C.c_int), ("pe_T0", C.c_int), ("pe_L2", C.c_int),
                 ("colsum", C.c_void_p), ("p", C.c_float), ("seed", C.c_uint64), ("site", C.c_uint), ("drop_ld", C.c_int64),
                 ("out", C.c_void_p), ("ldc", C.c_int64), ("out_f32", C.c_int), ("part_ws", C.c_void_p), ("part_ws_floats", C.c_size_t)]
+
+
+class AttnArgs(C.Structure):
+    """coot_attn_args: the whole attention descriptor (segments, packed rows, strides, dropout) for coot_debug_attn."""
+    _fields_ = [("q", C.c_void_p), ("ldq", C.c_int64), ("k", C.c_void_p), ("ldk", C.c_int64), ("v", C.c_void_p), ("ldv", C.c_int64),
+                ("o", C.c_void_p), ("ldo", C.c_int64), ("lse", C.c_void_p), ("lens", C.c_void_p),
+                ("Nseq", C.c_int), ("Lq", C.c_int), ("Lk", C.c_int), ("H", C.c_int), ("dh", C.c_int),
+                ("Nseq2", C.c_int), ("L2", C.c_int), ("lens2", C.c_void_p), ("cu", C.c_void_p),
+                ("dout", C.c_void_p), ("lddo", C.c_int64), ("delta", C.c_void_p),
+                ("dq", C.c_void_p), ("lddq", C.c_int64), ("dk", C.c_void_p), ("lddk", C.c_int64), ("dv", C.c_void_p), ("lddv", C.c_int64),
+                ("p", C.c_float), ("seed", C.c_uint64), ("site", C.c_uint)]
 
 
 class PackedSeqs(C.Structure):
@@ -277,6 +288,7 @@ def load():
     lib.coot_gemm_tn_workspace_bytes.argtypes = [i32, i32, i32]
     lib.coot_ln_fwd.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
     lib.coot_attn_fwd.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp]
+    lib.coot_debug_attn.argtypes = [C.POINTER(AttnArgs), i32, vp]
     lib.coot_probe_tr16.argtypes = [vp, vp]
     lib.coot_timing_enable.argtypes = [i32]
     lib.coot_timing_collect.argtypes = [i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)]

@@ -1069,6 +1069,37 @@ int coot_ln_fwd(const float* x, int R, int D, const float* gain, const float* bi
                 coot_stream_t stream);
 int coot_attn_fwd(const void* qkv, int Nseq, int L, int H, int dh, const int64_t* lens, void* out, float* lse,
                   coot_stream_t stream);
+/* The whole attention descriptor the networks use (tests): launch_attn_fwd (backward == 0) or launch_attn_bwd on it, so every
+ * dispatch path can be called alone: the one-query kernels (Lq == 1, Lk <= 64, one segment), the short kernels (Lq == Lk <= 128:
+ * optionally a second segment of Nseq2 sequences of length L2 whose rows start at row Nseq * Lk of every matrix, or packed rows:
+ * sequence n of both segments starts at row cu[n] and has lens[n] resp. lens2[n - Nseq] rows) and the chunked kernels (anything
+ * else, one segment).  Head h is columns [h dh, (h + 1) dh) of q, k, v, o, dout, dq, dk, dv; lse and delta are [rows, H] fp32.
+ * scale = 1 / sqrt(dh).  Keys >= lens[n] are filled with -32752 before the softmax over all Lk keys and pass no gradient; all Lq
+ * query rows are computed.  Dropout (p > 0) multiplies the probabilities by the mask of (seed, site) at mask row
+ * (n H + h) Lq + query, p quantised as coot_debug_attn_dropout_scales does; n counts within the segment, the second segment
+ * draws from seed + 0x9E3779B97F4A7C15, and a packed sequence uses its own length as Lq and Lk.  The backward reads o and lse
+ * (the forward's outputs), writes dq, dk, dv and uses delta as scratch.  Strides in elements, multiples of 8, base pointers
+ * 16-byte aligned.  lens[n] >= 1 is the caller's business (lens lives on the device): with every key filled the forward is
+ * uniform over Lk as in the reference, but the backward's dV is zero where the reference's is not.  coot_collate_level and
+ * coot_collate_packed do accept a sequence of 0 rows; the reference's dataset expands every segment to a minimum of frames. */
+typedef struct coot_attn_args {
+  const void* q; int64_t ldq;   /* bf16 [Nseq * Lq (+ Nseq2 * L2), >= H dh] */
+  const void* k; int64_t ldk;   /* bf16 [Nseq * Lk (+ Nseq2 * L2), >= H dh] */
+  const void* v; int64_t ldv;
+  void* o; int64_t ldo;         /* forward: output; backward: the saved output */
+  float* lse;                   /* fp32 [rows of q, H] */
+  const int64_t* lens;          /* [Nseq] valid keys */
+  int Nseq, Lq, Lk, H, dh;
+  int Nseq2, L2; const int64_t* lens2;
+  const int* cu;                /* packed rows: int32 [Nseq + Nseq2] first rows, or NULL */
+  const void* dout; int64_t lddo;
+  float* delta;                 /* fp32 [rows of q, H] scratch */
+  void* dq; int64_t lddq;
+  void* dk; int64_t lddk;
+  void* dv; int64_t lddv;
+  float p; uint64_t seed; unsigned site;
+} coot_attn_args;
+int coot_debug_attn(const coot_attn_args* a, int backward, coot_stream_t stream);
 /* HIP-event timing of every gemm_nt launch (the dominant kernel) while enabled; collect() synchronises the
  * recorded events and returns summed duration [ms], algorithmic flops (2*M*N*K) and launch count.
  * only_big_k != 0 restricts to the input-FC instances (K >= 1024). */
