@@ -679,6 +679,9 @@ int coot_get_option(const char* name, int* value) {
   if (!strcmp(name, "det_bypasses")) { *value = det_bypass_count(); return 0; }  // (see below)
   if (!strcmp(name, "det_overflows")) { *value = det_overflow_count(); return 0; }  // deterministic mode: shadow adds that wrapped under the guard (synchronises; -1: mode off)
   if (!strcmp(name, "det_overflow_check")) { *value = det_overflow_guard(); return 0; }  // deterministic mode: addends that took the float atomic (synchronises; -1: mode off)
+  if (!strcmp(name, "attn_bwd_loop")) { *value = get_attn_bwd_loop(); return 0; }
+  if (!strcmp(name, "attn_bwd_share")) { *value = get_attn_bwd_share(); return 0; }
+  if (!strcmp(name, "attn_bwd_grid")) { *value = get_attn_bwd_grid(); return 0; }
   if (!strcmp(name, "rt_topk_splits")) { *value = get_rt_topk_splits(); return 0; }
   if (!strcmp(name, "rt_few_splits")) { *value = get_rt_few_splits(); return 0; }
   if (!strcmp(name, "rt_grouped_splits")) { *value = get_rt_grouped_splits(); return 0; }
@@ -712,6 +715,9 @@ int coot_set_option(const char* name, int value) {
   if (!strcmp(name, "cl_small")) { set_cl_small(value); return 0; }
   if (!strcmp(name, "fz_debug")) { g_fz_debug = value; return 0; }
   if (!strcmp(name, "fused_min_rows")) { g_fused_min_rows = value; return 0; }
+  if (!strcmp(name, "attn_bwd_loop")) { set_attn_bwd_loop(value); return 0; }  // 1: the short attention backward loops over its (sequence, head) items in a fixed grid, the next item's loads in flight (attention.h; default 0, slower in the step)
+  if (!strcmp(name, "attn_bwd_share")) { set_attn_bwd_share(value); return 0; }  // 0: every lane of the short attention backward hashes its own dropout masks (attention.h; default 1: shared between the lanes of a key pair)
+  if (!strcmp(name, "attn_bwd_grid")) { set_attn_bwd_grid(value); return 0; }  // (tests) workgroups of the short attention backward's item loop, 0 = automatic; the result does not depend on it
   if (!strcmp(name, "rt_topk_splits")) { set_rt_topk_splits(value); return 0; }  // (tests) column splits of coot_retrieval_topk, 0 = automatic; the result does not depend on it
   if (!strcmp(name, "rt_few_splits")) { set_rt_few_splits(value); return 0; }  // (tests) row splits of coot_retrieval_topk_few, 0 = automatic; the result does not depend on it
   if (!strcmp(name, "rt_grouped_splits")) { set_rt_grouped_splits(value); return 0; }  // (tests) ranges of the group table in coot_retrieval_topk_grouped's selection, 0 = automatic; the result does not depend on it

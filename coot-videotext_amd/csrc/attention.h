@@ -39,5 +39,15 @@ int launch_attn_fwd(const AttnArgs& a, hipStream_t stream);
 int launch_attn_bwd(const AttnArgs& a, hipStream_t stream);
 // 1 (default): self-attention with L <= 128 uses the one-workgroup-per-(sequence, head) kernels; 0: chunked kernels (A/B switch)
 bool attn_short_path(int L);  // true if self-attention over sequences of length L takes the short kernels
+// short backward, A/B switches (attention.hip; every setting gives the same bytes):
+// attn_bwd_share 1 (default): phase B takes two of a tile's four mask hashes from the neighbouring lane, phase A hashes per pair of
+// keys; attn_bwd_loop 0 (default): one workgroup per (sequence, head), 1: a fixed grid of workgroups loops over the items with the
+// next item's loads in flight (slower in the train step, kept switched off)
+void set_attn_bwd_loop(int v);
+int get_attn_bwd_loop();
+void set_attn_bwd_share(int v);
+int get_attn_bwd_share();
+void set_attn_bwd_grid(int v);  // (tests) workgroups of the loop, 0 = automatic; the result does not depend on it
+int get_attn_bwd_grid();
 
 }  // namespace coot
