@@ -1,4 +1,4 @@
-// What the retrieval sources share (retrieval_tile.hip, retrieval_few.hip, retrieval_grouped.hip, retrieval_multi.hip, retrieval_scoped.hip, retrieval_index.hip): the chunk constants and the widening of a
+// What the retrieval sources share (retrieval_tile.hip, retrieval_few.hip, retrieval_grouped.hip, retrieval_multi.hip, retrieval_scoped.hip, retrieval_adjusted.hip, retrieval_index.hip): the chunk constants and the widening of a
 // gallery element, the 64-bit top-K entry and the fold of candidates into a sorted list, and the host helpers that carve a workspace
 // and turn a run-time value into a template argument.  Every kernel is instantiated in one file only.
 #pragma once

@@ -16,6 +16,9 @@ retrieval_topk_grouped_device / GalleryIndex.search_grouped: the K best GROUPS o
 groups for a PARAGRAPH of queries (compute_retrieval_topk_multi): coot_retrieval_topk_multi.  retrieval_topk_scoped_device /
 GalleryIndex.search_scoped: every query inside (only=) or outside (exclude=) the rows with the id it brings
 (compute_retrieval_topk_scoped): coot_retrieval_topk_scoped; GalleryIndex.neighbors: a row's neighbours outside its own group.
+retrieval_topk_adjusted_device / GalleryIndex.search_adjusted: a number per gallery row taken off its similarity before the selection
+(compute_retrieval_topk_adjusted): coot_retrieval_topk_adjusted; GalleryIndex.hubness_offsets: the offsets that make it rank by CSLS
+(compute_retrieval_hub_offsets): coot_retrieval_knn_join against a bank of queries, then coot_retrieval_hub_offsets.
 retrieval_range_device / GalleryIndex.search_range, count_range: every row at or above a query's threshold, however many, as CSR
 (compute_retrieval_range): coot_retrieval_range_count, _scan, _fill for up to RANGE_TILE_MIN_M* - 1 queries, in slices of 16, and
 coot_retrieval_range_tile_count, _scan, _tile_fill from there on, one call per pass (_range).
@@ -30,7 +33,7 @@ per chunk of left rows, under the same budget (_cross_join).
 retrieval_knn_join_device / GalleryIndex.knn_join, knn_graph: the k best partners of EVERY row of an index, in a second index or in
 itself, under the joins' filters (compute_retrieval_knn_join): one call of coot_retrieval_knn_join, both sides read as stored (_knn_join).
 The searches on a prepared gallery share one host check (_check_search) and have one implementation per library call (_topk_few,
-_topk_tile, _topk_grouped, _topk_multi, _topk_scoped), which the public wrapper and the GalleryIndex method both call.
+_topk_tile, _topk_grouped, _topk_multi, _topk_scoped, _topk_adjusted), which the public wrapper and the GalleryIndex method both call.
 GalleryIndex.add / update / compact: rows appended or overwritten in place together with their norms (coot_retrieval_rows_put),
 removed rows dropped — the index then holds, byte for byte, what a fresh index on the same rows holds.
 
@@ -45,7 +48,7 @@ from .retrieval_mirror import (VALKEYS, _ahead, _host_offsets, _labeled_metrics,
                                compute_retrieval_counts_part, compute_retrieval_labeled, compute_retrieval_topk, compute_retrieval_topk_grouped,
                                compute_retrieval_range, compute_retrieval_topk_masked, compute_retrieval_topk_multi, compute_retrieval_topk_scoped,
                                compute_retrieval_self_join, compute_retrieval_components, compute_retrieval_join, compute_retrieval_knn_join,
-                               strip_bounds)
+                               compute_retrieval_topk_adjusted, compute_retrieval_hub_offsets, strip_bounds)
 
 
 def _ptr(t):
@@ -385,6 +388,75 @@ def retrieval_topk_scoped_device(queries, gallery, norms, groups, k: int, only=N
     or not; without it, blocks of 128 rows in which no row is eligible for any query of a slice are not read.  Nothing synchronises.
     More than 16 queries run in slices of 16, one sweep of the gallery each, over one workspace."""
     return _topk_scoped(queries, gallery, norms, groups, k, only, exclude, keep, want_sim)
+
+
+def _check_offset(fn: str, offset, n: int, dev):
+    """The offset of an adjusted search, checked on the host before anything is launched (ValueError): a cuda torch.float32 tensor [N]
+    on the gallery's device (dev), or N numbers on the host (a sequence, a numpy array or a CPU tensor).  Returns the cuda tensor, or a
+    float32 numpy array [N] that the caller uploads once: a host value is rounded to float32 here, once."""
+    import torch
+    if isinstance(offset, torch.Tensor) and offset.is_cuda:
+        if offset.dtype is not torch.float32:
+            raise ValueError(f"{fn}: offset on the device has to be torch.float32, not {offset.dtype}")
+        if tuple(offset.shape) != (n,):
+            raise ValueError(f"{fn}: offset of shape {tuple(offset.shape)}, a gallery of {n} rows (one number per row: [{n}])")
+        if offset.device != dev:
+            raise ValueError(f"{fn}: offset lives on {offset.device}, the gallery on {dev}")
+        return offset
+    try:
+        t = np.asarray(offset.numpy() if isinstance(offset, torch.Tensor) else offset)
+    except Exception:
+        t = np.asarray(None)
+    if t.dtype.kind not in "fiu":
+        raise ValueError(f"{fn}: offset has to hold one number per gallery row, not dtype {t.dtype}")
+    if t.shape != (n,):
+        raise ValueError(f"{fn}: offset of shape {tuple(t.shape)}, a gallery of {n} rows (one number per row: [{n}])")
+    with np.errstate(over="ignore"):
+        return np.array(t.astype(np.float32))  # (a copy: contiguous and writable)
+
+
+def _topk_adjusted(queries, gallery, norms, offset, k: int, keep, want_sim: bool, method=None, own_keep=None):
+    """coot_retrieval_topk_adjusted for any M: slices of RETRIEVAL_FEW_MAX queries over one workspace.  Checked in this order: keep, the
+    offset, then where everything lives, the widths and k.  method, own_keep: the name and the own filter of GalleryIndex.search_adjusted."""
+    import torch
+    from . import lib as _lib
+    fn = "retrieval_topk_adjusted_device"
+    who = method or fn
+    assert gallery.dim() == 2, gallery.shape
+    if keep is not None:
+        keep = _check_keep(who, keep, gallery.shape[0], mirror=None)
+    offset = _check_offset(who, offset, gallery.shape[0], gallery.device)
+    queries = queries[None] if queries.dim() == 1 else queries
+    (queries, gallery, norms), code, (m, n, d, k) = _check_search(fn, "compute_retrieval_topk_adjusted", queries, gallery, norms, k, queries.dtype,
+                                                                  also=(keep,), method=method)
+    offset = torch.from_numpy(offset).to(queries.device) if isinstance(offset, np.ndarray) else offset.contiguous()
+    keep = _and_own(own_keep, keep)
+    lib = _lib.load()
+    ws, idx, scores, sim = _topk_buffers(lib.coot_retrieval_topk_adjusted_workspace_bytes(min(m, RETRIEVAL_FEW_MAX), n, d, k), m, n, k, want_sim,
+                                         queries.device)
+    st = _stream()
+    for i in range(0, m, RETRIEVAL_FEW_MAX):  # the calls of a stream run in order: one workspace
+        mm = min(RETRIEVAL_FEW_MAX, m - i)
+        _lib.check(lib.coot_retrieval_topk_adjusted(queries[i:].data_ptr(), gallery.data_ptr(), code, _ptr(norms), _ptr(keep), offset.data_ptr(), mm, n,
+                                                    d, k, idx[i:].data_ptr(), scores[i:].data_ptr(), sim[i:].data_ptr() if want_sim else None,
+                                                    ws.data_ptr(), ws.numel(), st), "coot_retrieval_topk_adjusted")
+    return idx, scores, sim
+
+
+def retrieval_topk_adjusted_device(queries, gallery, norms, offset, k: int, keep=None, want_sim: bool = False):
+    """The adjusted search on a gallery as a prepared index holds it (coot_retrieval_topk_adjusted): every gallery row brings a number
+    that is taken off its similarity before the selection.  queries cuda float32 [M, d], gallery cuda float32, bfloat16 or float16
+    [N, d], norms cuda float32 [N] (GalleryIndex.norms) or None: rows used as they are; offset: a cuda torch.float32 tensor [N], or N
+    numbers on the host (a sequence, a numpy array or a CPU tensor), rounded to float32 once and uploaded once.  Returns (idx int32
+    [M, k], scores float32 [M, k], sim [M, N] or None) on the device: the k best rows that keep lets pass by a(i, j) = s(i, j) -
+    offset[j], one float32 subtraction on the similarity s the other searches select from, in their order (a descending, then the
+    larger row); scores holds the bytes of a, sim (a testing aid) the raw s of every row, kept or not.
+    compute_retrieval_topk_adjusted of those similarities, byte for byte; with offset = 0 the bytes of the filtered search.  A row with
+    offset +inf scores -inf and is still returned, with its index, once nothing better is left (a masked row never is); -inf puts a
+    row first.  With fewer than k kept rows the tail is idx -1, score -inf.  1 <= k <= min(N, 128), whatever keep holds.  Without
+    sim, blocks of 128 rows in which keep leaves no row are not read.  Nothing synchronises.  More than 16 queries run in slices of
+    16, one sweep of the gallery each, over one workspace."""
+    return _topk_adjusted(queries, gallery, norms, offset, k, keep, want_sim)
 
 
 RETRIEVAL_RANGE_BLOCK = 128  # include/coot_hip.h: COOT_RETRIEVAL_RANGE_BLOCK
@@ -1010,6 +1082,9 @@ class GalleryIndex:
     logical AND.  Removed rows still occupy memory until compact(): the gallery bytes and the norms are untouched, only the selection
     skips them.
 
+    Offsets.  search_adjusted(queries, k, offset) ranks by the similarity minus a number per row, and hubness_offsets(bank) computes
+    the numbers that correct hubness (CSLS) from a second index of representative queries: see the methods.
+
     Range search.  search_range(queries, threshold) returns every row at or above a query's threshold, however many, as CSR (offsets,
     rows, scores), and count_range their number: see the methods.  keep and the index's own filter apply as in search.
     self_join(threshold) is the same question about the gallery itself: all pairs of rows at or above a threshold, each once;
@@ -1286,6 +1361,46 @@ class GalleryIndex:
         index does not store groups; the caller owns the table across add() and compact(), as in search_grouped."""
         return _topk_scoped(queries, self.gallery, self.norms if self.normalize else None, groups, k, only, exclude, keep, want_sim,
                             method="GalleryIndex.search_scoped", own_keep=self.keep)
+
+    def search_adjusted(self, queries, k: int, offset, keep=None, want_sim: bool = False):
+        """The k best rows for every query after A NUMBER PER ROW has been taken off its similarity: (idx int32 [M, k], scores
+        float32 [M, k], sim [M, N] or None) on the device.  offset: a cuda torch.float32 tensor [index.n], or index.n numbers on the
+        host (a sequence, a numpy array or a CPU tensor; rounded to float32 and uploaded once).  Rows are ranked by a(i, j) =
+        s(i, j) - offset[j], one float32 subtraction on the similarity search() ranks on, bit for bit, in search()'s order (a
+        descending, then the larger row); scores holds the bytes of a, sim the raw s of every row, the bytes of search(queries, k,
+        want_sim=True)[2].  Exact: compute_retrieval_topk_adjusted of those similarities, byte for byte, for every storage type and
+        whatever else is in the batch; with offset = 0 the bytes of search(queries, k, keep=keep).  What search(queries, 128), a
+        subtraction and a re-sort cannot give, because a row outside the raw top 128 may be inside the adjusted top k.
+        index.hubness_offsets(bank) is the offset that corrects hubness (CSLS): search_adjusted(q, k, index.hubness_offsets(bank));
+        a recency boost, a popularity prior or a calibration constant per source are offsets too.  offset +inf leaves a row with
+        score -inf, still a row and returned last (ties to the larger row), unlike a masked one; -inf puts it first.  keep and the
+        index's own filter (remove) combine as in search; with fewer than k kept rows the tail is idx -1, score -inf.  1 <= k <=
+        min(N, 128).  Nothing synchronises.  Any M: slices of 16 queries, one sweep of the gallery each
+        (retrieval_topk_adjusted_device).  The index does not store offsets; the caller owns the vector across add() (append to it)
+        and compact() (offset[old_rows]), as for groups in search_grouped."""
+        return _topk_adjusted(queries, self.gallery, self.norms if self.normalize else None, offset, k, keep, want_sim,
+                              method="GalleryIndex.search_adjusted", own_keep=self.keep)
+
+    def hubness_offsets(self, bank, k: int = 10, keep=None, other_keep=None):
+        """The offsets that make search_adjusted rank by CSLS, a correction of HUBNESS (rows close to the common direction of all
+        queries, which are top-1 for many queries they do not belong to): a cuda float32 [index.n], offsets[j] = half the mean
+        similarity of row j to its k nearest rows of `bank`, a GalleryIndex of representative queries (the training captions) with
+        the same width, normalize and device (TypeError / ValueError before anything is launched, as in knn_join).  CSLS is
+        2 s(i, j) - r_q(i) - r_g(j); r_q is constant per query, so query i ranks by s(i, j) - r_g(j) / 2.
+        self.knn_join(bank, k, keep=keep, other_keep=other_keep), then one launch of coot_retrieval_hub_offsets: per row the scores of
+        the filled slots added in rank order in float32, divided by their number and halved; a row that keep or the index's own
+        filter masks, and every row when no bank row is eligible, gets 0.  compute_retrieval_hub_offsets of knn_join's output, byte
+        for byte.  1 <= k <= min(len(bank), 128).  Nothing synchronises."""
+        import torch
+        from . import lib as _lib
+        who = "GalleryIndex.hubness_offsets"
+        self._check_right(who, bank)
+        idx, scores = _knn_join(self.gallery, self.norms if self.normalize else None, bank.gallery, bank.norms if bank.normalize else None, k, keep,
+                                other_keep, None, None, False, method=who, own_keep=self.keep, other_own_keep=bank.keep)
+        out = torch.empty(idx.shape[0], dtype=torch.float32, device=idx.device)
+        _lib.check(_lib.load().coot_retrieval_hub_offsets(scores.data_ptr(), idx.data_ptr(), idx.shape[0], idx.shape[1], out.data_ptr(), _stream()),
+                   "coot_retrieval_hub_offsets")
+        return out
 
     def search_range(self, queries, threshold, keep=None, max_results=None, order: str = "row"):
         """EVERY row that scores at least the query's threshold, however many there are: (offsets int64 [M + 1], rows int32 [T], scores

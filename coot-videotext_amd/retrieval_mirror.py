@@ -7,6 +7,8 @@ compute_retrieval_topk (_masked, _grouped, _multi, _scoped): WHICH gallery items
 on a similarity matrix [M, N], M and N independent; under a keep flag per gallery row; the K best GROUPS of rows, each through its
 best row; the K best groups for a PARAGRAPH of queries (MaxSim), whose offsets _host_offsets checks for mirror and device wrappers
 alike; under a mask per QUERY, the rows with (only) or without (exclude) the id the query brings.
+compute_retrieval_topk_adjusted: compute_retrieval_topk_masked after a number per column has been taken off every similarity.
+compute_retrieval_hub_offsets: the lists of a k-NN join into such a number per row, half the mean score of its filled slots (CSLS).
 compute_retrieval_range: every column at or above a row's threshold, however many, as CSR.
 compute_retrieval_self_join: the same on a gallery's similarities with itself, read as pairs: the columns right of the diagonal.
 compute_retrieval_components: the connected components of those pairs, a cluster label per row: a plain host union-find.
@@ -127,6 +129,41 @@ def compute_retrieval_topk_scoped(sim: np.ndarray, k: int, groups, only=None, ex
     for i in range(m):
         idx[i], scores[i] = compute_retrieval_topk_masked(sim[i:i + 1], k, ok & ((groups == scope[i]) == (only is not None)))
     return idx, scores
+
+
+def compute_retrieval_topk_adjusted(sim: np.ndarray, offset, k: int, keep=None) -> Tuple[np.ndarray, np.ndarray]:
+    """The k best columns of every row of sim [M, N] by a(i, j) = sim[i, j] - offset[j], one float32 subtraction: (idx int32 [M, k],
+    scores float32 [M, k]), scores the values of a.  offset: [N] numbers, rounded to float32 once.  compute_retrieval_topk_masked of a
+    under keep ([N] booleans or bytes), compute_retrieval_topk of a without it: a descending, then column descending; with fewer
+    than k kept columns the tail is idx -1, score -inf.  offset +inf gives a = -inf, still a column (unlike a masked one); -inf puts
+    the column first.  A NaN in a (inf - inf) is not modelled."""
+    sim = np.asarray(sim)
+    with np.errstate(over="ignore"):
+        offset = np.asarray(offset).astype(np.float32)
+    assert sim.ndim == 2 and sim.dtype == np.float32 and offset.shape == (sim.shape[1],), (sim.shape, sim.dtype, offset.shape)
+    with np.errstate(invalid="ignore"):
+        a = (sim - offset[None, :]).astype(np.float32)
+    return compute_retrieval_topk(a, k) if keep is None else compute_retrieval_topk_masked(a, k, keep)
+
+
+def compute_retrieval_hub_offsets(scores: np.ndarray, idx: np.ndarray) -> np.ndarray:
+    """The lists of compute_retrieval_knn_join (scores float32 [N, k], idx [N, k]: every row of a gallery against a bank of queries)
+    into one offset per row, float32 [N].  Per row j: c = the number of slots with idx >= 0 (the filled ones, a prefix); c > 0: acc =
+    0, acc += scores[j, t] for t = 0 .. c - 1 in that order in float32, out[j] = 0.5 * (acc / c) in float32; c == 0: out[j] = 0.  An
+    explicit loop: np.sum and np.mean add pairwise.  With it as the offset compute_retrieval_topk_adjusted ranks by CSLS,
+    2 s(i, j) - r_q(i) - r_g(j), for every query i."""
+    scores, idx = np.asarray(scores), np.asarray(idx)
+    assert scores.ndim == 2 and scores.dtype == np.float32 and idx.shape == scores.shape, (scores.shape, scores.dtype, idx.shape)
+    out = np.zeros(scores.shape[0], np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for j in range(scores.shape[0]):
+            c = int((idx[j] >= 0).sum())
+            if c:
+                acc = np.float32(0)
+                for t in range(c):
+                    acc = np.float32(acc + scores[j, t])
+                out[j] = np.float32(0.5) * np.float32(acc / np.float32(c))
+    return out
 
 
 def compute_retrieval_range(sim: np.ndarray, threshold, keep=None, order: str = "row") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:

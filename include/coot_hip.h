@@ -524,6 +524,40 @@ int coot_retrieval_topk_scoped(const float* queries, const void* gallery, int ga
                                const int32_t* groups, const int32_t* scope, int exclude, int M, int N, int d, int K, int32_t* idx_out,
                                float* score_out, float* sim_out, void* workspace, size_t workspace_bytes, coot_stream_t stream);
 
+/* ---- adjusted search: a number per gallery row is taken off its similarity before the selection -----------------------------------
+ * offset: device fp32 [N].  The adjusted score is a(i, j) = s(i, j) - offset[j], one IEEE fp32 subtraction after the chain, where
+ * s(i, j) is the fp32 similarity every search here ranks on, bit for bit the sim_out of coot_retrieval_topk_few_masked.  idx_out,
+ * score_out [M, K]: the K best rows of every query that pass keep (NULL: no filter) by a, in the order of every search (a descending,
+ * then the larger row), and the bytes of a; idx -1 / score -inf in the slots that fewer than K kept rows leave unfilled.  offset[j] =
+ * +inf gives a = -inf: the row is still a row and is returned with its index once nothing better is left, ties at -inf going to the
+ * larger row; offset[j] = -inf puts the row first; a NaN is ordered as a NaN similarity is.  sim_out [M, N], optional: the raw s of
+ * every row, kept or not.  A hubness correction (coot_retrieval_hub_offsets: CSLS), a recency boost, a popularity prior or a
+ * calibration constant per source are all such an offset.
+ *   1 <= M <= COOT_RETRIEVAL_FEW_MAX, 1 <= K <= min(N, 128) (K is not checked against the mask);
+ *   gallery_dtype COOT_GALLERY_F32, _BF16 or _F16; gallery_norms NULL: rows used as they are.
+ * One sweep of the gallery serves all M queries, the few-query search's with one more 4-byte load per row.  Without sim_out a block of
+ * 128 rows in which keep leaves no row is not read at all.  The result depends on neither a query's batch-mates, the storage type
+ * (beyond the exact widening) nor the sweep's row splits (coot_set_option("rt_few_splits", n)).  workspace (16-byte aligned):
+ * coot_retrieval_topk_adjusted_workspace_bytes(M, N, d, K), the few-query search's layout; it needs no device, does not depend on the
+ * option and is 256 for arguments out of range.  A refused call (unknown dtype, null pointer other than gallery_norms, keep and
+ * sim_out, M or K outside its range, workspace misaligned or too small) returns before any launch and writes nothing.  No allocation,
+ * no synchronisation; no pointer is retained. */
+size_t coot_retrieval_topk_adjusted_workspace_bytes(int M, int N, int d, int K);
+int coot_retrieval_topk_adjusted(const float* queries, const void* gallery, int gallery_dtype, const float* gallery_norms, const uint8_t* keep,
+                                 const float* offset, int M, int N, int d, int K, int32_t* idx_out, float* score_out, float* sim_out,
+                                 void* workspace, size_t workspace_bytes, coot_stream_t stream);
+
+/* ---- hubness offsets: the lists of a k-NN join into one number per row ---------------------------------------------------------------
+ * scores (fp32), idx (int32): device [N][K], the lists coot_retrieval_knn_join wrote for the N gallery rows against a bank of
+ * representative queries.  Per row j: c = the number of slots with idx >= 0 (the filled ones, a prefix); c > 0: acc = 0, then
+ * acc += scores[j][t] for t = 0 .. c - 1 in that order, in fp32, and out[j] = 0.5f * (acc / (float)c); c == 0 (a masked row, or no
+ * bank row eligible): out[j] = 0.  out: device fp32 [N], half the mean similarity of row j to its k nearest bank rows: with it as
+ * the offset, coot_retrieval_topk_adjusted ranks by CSLS, 2 s(i, j) - r_q(i) - r_g(j), whose r_q is constant per query.  The bytes are
+ * defined: one thread per row, no reassociation, no transcendental.  1 <= N, 1 <= K <= 128.  One launch; a refused call (null pointer,
+ * N or K outside its range) returns before it and writes nothing.  No workspace, no allocation, no synchronisation; no pointer is
+ * retained. */
+int coot_retrieval_hub_offsets(const float* scores, const int32_t* idx, int N, int K, float* out, coot_stream_t stream);
+
 /* ---- range search: every gallery row at or above a query's threshold ------------------------------------------------------------
  * Row j is a hit of query i when it passes keep (NULL: no filter) and s(i, j) >= thresholds[i], an IEEE fp32 compare: a NaN score or a
  * NaN threshold is no hit, -0 >= +0 holds, -inf returns every kept row whose score is not a NaN, +inf only rows that score +inf.
