@@ -215,6 +215,124 @@ int coot_debug_attn(const coot_attn_args* a, int backward, coot_stream_t stream)
   }
   return backward ? launch_attn_bwd(g, (hipStream_t)stream) : launch_attn_fwd(g, (hipStream_t)stream);
 }
+// tests: the LayerNorm descriptors as the networks fill them (api.hip); part_ws is the launcher's business (set_partials_workspace)
+int coot_debug_ln(const coot_ln_args* a, int backward, coot_stream_t stream) {
+  COOT_REQUIRE(a, "debug_ln: null arguments");
+  COOT_REQUIRE(a->x && a->R >= 0, "debug_ln: null source or negative R");
+  COOT_REQUIRE(a->D >= 8 && a->D % 4 == 0 && a->D <= (backward ? 1024 : 4096), "debug_ln: D=%d unsupported (multiple of 4, 8 .. %d)", a->D,
+               backward ? 1024 : 4096);
+  const int64_t D = a->D;
+  COOT_REQUIRE(a->ldx >= D && a->ldx % 4 == 0, "debug_ln: ldx must be a multiple of 4 and at least D");
+  COOT_REQUIRE(a->p >= 0.f && a->p < 1.f && a->pm >= 0.f && a->pm < 1.f, "debug_ln: 0 <= p < 1");
+  if (!backward) {
+    COOT_REQUIRE(a->y || a->y32, "debug_ln: no output");
+    COOT_REQUIRE((!a->y || (a->ldy >= D && a->ldy % 4 == 0)) && (!a->y32 || (a->ldy32 >= D && a->ldy32 % 4 == 0)),
+                 "debug_ln: output strides must be multiples of 4 and at least D");
+    COOT_REQUIRE(!a->gain || a->bias, "debug_ln: gain needs bias");
+    COOT_REQUIRE(!a->pe || a->pe_L >= 1, "debug_ln: pe needs pe_L >= 1");
+    COOT_REQUIRE(!a->x2 || (a->R0 >= 0 && a->R0 <= a->R), "debug_ln: R0 outside 0 .. R");
+    COOT_REQUIRE(!a->cu || (a->nseq >= 1 && (a->src_packed || (a->N0 >= 0 && a->L0 >= 1 && (a->N0 >= a->nseq || (a->x2 && a->L1 >= 1))))),
+                 "debug_ln: packed rows need nseq >= 1 and, with a padded source, N0, L0 (and x2, L1 for sequences >= N0)");
+    COOT_REQUIRE(a->cu || (!a->pos_out && !a->src_packed), "debug_ln: pos_out / src_packed need cu");
+    COOT_REQUIRE(a->max_wgs >= 0, "debug_ln: max_wgs < 0");
+    LnFwd l; l.x = a->x; l.x_f32 = a->x_f32 ? 1 : 0; l.ldx = a->ldx; l.x2 = a->x2; l.R0 = a->R0; l.R = a->R; l.D = a->D;
+    l.gain = a->gain; l.bias = a->bias; l.pe = a->pe; l.pe_L = a->pe ? a->pe_L : 1;
+    l.y = (bf16_t*)a->y; l.ldy = a->ldy; l.y32 = a->y32; l.ldy32 = a->ldy32;
+    l.drop = make_drop(1, a->p, a->seed, a->site, nullptr);
+    l.cu = a->cu; l.nseq = a->nseq; l.N0 = a->N0; l.L0 = a->L0; l.L1 = a->L1; l.pos_out = a->pos_out; l.src_packed = a->src_packed ? 1 : 0;
+    l.max_wgs = a->max_wgs; l.nt = a->nt ? 1 : 0;
+    return launch_ln_fwd(l, (hipStream_t)stream);
+  }
+  COOT_REQUIRE((a->dy || a->dy32) && a->gain, "debug_ln: backward: null pointer");
+  COOT_REQUIRE((!a->dy || a->dy32 || (a->lddy >= D && a->lddy % 4 == 0)) && (!a->dy32 || (a->lddy32 >= D && a->lddy32 % 4 == 0)) &&
+               (!a->dy_add || (a->lddy_add >= D && a->lddy_add % 4 == 0)), "debug_ln: backward: gradient strides must be multiples of 4 and at least D");
+  COOT_REQUIRE((!a->dx || (a->lddx >= D && a->lddx % 4 == 0)) && (!a->dx32 || (a->lddx32 >= D && a->lddx32 % 4 == 0)) &&
+               (!a->dxm || (a->lddxm >= D && a->lddxm % 4 == 0)), "debug_ln: backward: output strides must be multiples of 4 and at least D");
+  COOT_REQUIRE(!(a->dxm && a->pm > 0.f) || (a->dxm_drop_ld >= D && a->dxm_drop_ld % 2 == 0), "debug_ln: backward: dxm_drop_ld must be even and at least D");
+  COOT_REQUIRE(!a->part_ws || a->part_ws_floats > 0, "debug_ln: part_ws without part_ws_floats");
+  LnBwd b; b.dy = (const bf16_t*)a->dy; b.lddy = a->lddy; b.dy32 = a->dy32; b.lddy32 = a->lddy32; b.dy_add = (const bf16_t*)a->dy_add; b.lddy_add = a->lddy_add;
+  b.x = a->x; b.x_f32 = a->x_f32 ? 1 : 0; b.ldx = a->ldx; b.gain = a->gain; b.R = a->R; b.D = a->D;
+  b.dx = (bf16_t*)a->dx; b.lddx = a->lddx; b.dx32 = a->dx32; b.lddx32 = a->lddx32; b.dxm = (bf16_t*)a->dxm; b.lddxm = a->lddxm;
+  b.dxm_drop = make_drop(1, a->pm, a->seed_m, a->site_m, nullptr); b.dxm_drop_ld = a->dxm_drop_ld;
+  b.dgain = a->dgain; b.dbias = a->dbias; b.dxcolsum = a->dxcolsum;
+  b.drop = make_drop(1, a->p, a->seed, a->site, nullptr);
+  if (a->part_ws) set_partials_workspace(a->part_ws, a->part_ws_floats);
+  const int rc = launch_ln_bwd(b, (hipStream_t)stream);
+  if (a->part_ws) set_partials_workspace(nullptr, 0);
+  return rc;
+}
+// tests: one or two GenPool segments as pool_all (api.hip) fills them; defer: the backward's column sum inside a deferred-reduction scope
+int coot_debug_pool(const coot_pool_args* segs, int nseg, int backward, float* part_ws, size_t part_ws_floats, int defer, coot_stream_t stream) {
+  COOT_REQUIRE(segs, "debug_pool: null arguments");
+  COOT_REQUIRE(nseg >= 1 && nseg <= 2, "debug_pool: one or two segments");
+  COOT_REQUIRE(!part_ws || part_ws_floats > 0, "debug_pool: part_ws without part_ws_floats");
+  COOT_REQUIRE(!defer || (backward && part_ws), "debug_pool: defer needs the backward and a workspace");
+  PoolArgs g[2];
+  for (int i = 0; i < nseg; ++i) {
+    const coot_pool_args& a = segs[i];
+    const int64_t D = a.D;
+    COOT_REQUIRE(a.s && a.z && a.lens && a.pooled, "debug_pool: null pointer");
+    COOT_REQUIRE(a.D >= 64 && a.D <= 512 && a.D % 8 == 0 && a.D == segs[0].D, "debug_pool: D=%d unsupported (multiple of 8, 64 .. 512, the same in both segments)", a.D);
+    COOT_REQUIRE(a.N >= 1 && (a.cu || a.L >= 1), "debug_pool: N and L must be positive");
+    COOT_REQUIRE(a.lds >= D && a.lds % 8 == 0 && a.ldz >= D && a.ldz % 8 == 0 && a.ldp >= D, "debug_pool: strides must be multiples of 8 (ldp: any) and at least D");
+    COOT_REQUIRE(a.p_w >= 0.f && a.p_w < 1.f && a.p_s >= 0.f && a.p_s < 1.f, "debug_pool: 0 <= p < 1");
+    COOT_REQUIRE(!a.smax == !a.ssum, "debug_pool: smax and ssum go together");
+    if (a.pk_out) COOT_REQUIRE(!backward && a.pk_counts && a.pk_B >= 1 && a.pk_Cmax >= 1, "debug_pool: the hand-over needs pk_counts, pk_B, pk_Cmax (forward only)");
+    if (backward) {
+      COOT_REQUIRE(a.dpooled && a.ds && a.dz && a.smax && a.ssum, "debug_pool: backward: null pointer");
+      COOT_REQUIRE(a.lddp >= D && a.ldds >= D && a.ldds % 8 == 0 && a.lddz >= D && a.lddz % 8 == 0, "debug_pool: backward: strides must be multiples of 8 (lddp: any) and at least D");
+      COOT_REQUIRE(!(a.p_s > 0.f) || (a.drop_s_ld >= D && a.drop_s_ld % 2 == 0 && a.drop_s_row0 >= 0), "debug_pool: backward: drop_s_ld must be even and at least D, drop_s_row0 >= 0");
+      COOT_REQUIRE(a.ds_colsum == segs[0].ds_colsum, "debug_pool: backward: the segments share ds_colsum");
+    }
+    PoolArgs& p = g[i];
+    p.s = (const bf16_t*)a.s; p.lds = a.lds; p.z = (const bf16_t*)a.z; p.ldz = a.ldz; p.lens = (const long long*)a.lens; p.cu = a.cu;
+    p.N = a.N; p.L = a.L; p.D = a.D; p.pooled = a.pooled; p.ldp = a.ldp; p.pooled_copy = a.pooled_copy; p.smax = a.smax; p.ssum = a.ssum;
+    p.drop_w = make_drop(1, a.p_w, a.seed_w, a.site_w, nullptr);
+    if (backward) {
+      p.dpooled = a.dpooled; p.lddp = a.lddp; p.ds = (bf16_t*)a.ds; p.ldds = a.ldds; p.dz = (bf16_t*)a.dz; p.lddz = a.lddz; p.ds_colsum = a.ds_colsum;
+      p.drop_s = make_drop(1, a.p_s, a.seed_s, a.site_s, nullptr); p.drop_s_ld = a.drop_s_ld; p.drop_s_row0 = a.drop_s_row0;
+    } else if (a.pk_out) {
+      p.pk_counts = (const long long*)a.pk_counts; p.pk_B = a.pk_B; p.pk_Cmax = a.pk_Cmax; p.pk_out = a.pk_out; p.pk_mask = a.pk_mask; p.pk_lens = (long long*)a.pk_lens;
+    }
+  }
+  if (part_ws) set_partials_workspace(part_ws, part_ws_floats);
+  int rc;
+  if (!backward) rc = launch_pool_fwd2(g, nseg, (hipStream_t)stream);
+  else if (!defer) rc = launch_pool_bwd2(g, nseg, (hipStream_t)stream);
+  else {
+    colsum_defer_begin();
+    rc = launch_pool_bwd2(g, nseg, (hipStream_t)stream);
+    if (!rc) rc = colsum_defer_flush((hipStream_t)stream);
+    colsum_defer_end();
+  }
+  if (part_ws) set_partials_workspace(nullptr, 0);
+  return rc;
+}
+int coot_debug_avgpool(const void* z, int64_t ldz, const int64_t* lens, int N, int L, int D, float* out, int64_t ldo, coot_stream_t stream) {
+  COOT_REQUIRE(z && lens && out, "debug_avgpool: null pointer");
+  COOT_REQUIRE(N >= 0 && L >= 1 && D >= 2 && D % 2 == 0 && ldz >= D && ldz % 2 == 0 && ldo >= D, "debug_avgpool: D even, ldz even, strides at least D");
+  return launch_avgpool_fwd((const bf16_t*)z, ldz, (const long long*)lens, N, L, D, out, ldo, (hipStream_t)stream);
+}
+int coot_debug_avgpool_bwd(const float* dpooled, int64_t lddp, const int64_t* lens, int N, int L, int D, void* dz, int64_t lddz, coot_stream_t stream) {
+  COOT_REQUIRE(dpooled && lens && dz, "debug_avgpool_bwd: null pointer");
+  COOT_REQUIRE(N >= 0 && L >= 1 && D >= 2 && D % 2 == 0 && lddz >= D && lddz % 2 == 0 && lddp >= D, "debug_avgpool_bwd: D even, lddz even, strides at least D");
+  return launch_avgpool_bwd(dpooled, lddp, (const long long*)lens, N, L, D, (bf16_t*)dz, lddz, (hipStream_t)stream);
+}
+int coot_debug_pack_bwd_join(const float* dout1, const float* dout2, const float* dctx, const int64_t* counts, int B, int Cmax, int D,
+                             float* demb_items, float* demb_ctx, coot_stream_t stream) {
+  COOT_REQUIRE(dout1 && counts && demb_items && (!dctx || demb_ctx), "debug_pack_bwd_join: null pointer");
+  COOT_REQUIRE(B >= 0 && Cmax >= 1 && D >= 1, "debug_pack_bwd_join: B >= 0, Cmax >= 1, D >= 1");
+  return launch_pack_bwd_join(dout1, dout2, dctx, (const long long*)counts, B, Cmax, D, demb_items, demb_ctx, (hipStream_t)stream);
+}
+int coot_debug_colsum_bf16(const void* x, int64_t ldx, int R, int C, float* out, float* part_ws, size_t part_ws_floats, coot_stream_t stream) {
+  COOT_REQUIRE(x && out, "debug_colsum_bf16: null pointer");
+  COOT_REQUIRE(R >= 0 && C >= 2 && C % 2 == 0 && ldx >= C && ldx % 2 == 0, "debug_colsum_bf16: C even, ldx even and at least C");
+  COOT_REQUIRE(!part_ws || part_ws_floats > 0, "debug_colsum_bf16: part_ws without part_ws_floats");
+  if (part_ws) set_partials_workspace(part_ws, part_ws_floats);
+  const int rc = launch_colsum_bf16((const bf16_t*)x, ldx, R, C, out, (hipStream_t)stream);
+  if (part_ws) set_partials_workspace(nullptr, 0);
+  return rc;
+}
 size_t coot_gemm_tn_workspace_bytes(int T, int Mo, int No) { return gemm_tn_workspace_floats(T, Mo, No, 1) * sizeof(float); }
 int coot_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, int T, int Mo, int No, float* C, int64_t ldc,
                  void* workspace, size_t workspace_bytes, coot_stream_t stream) {

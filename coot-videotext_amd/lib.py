@@ -27,7 +27,7 @@ EXPORTS = [
     "coot_net_param_info", "coot_net_out_dim", "coot_net_wpack_bytes", "coot_net_pack_weights", "coot_nets_pack_weights",
     "coot_net_saved_bytes", "coot_net_scratch_bytes", "coot_net_fwd", "coot_net_bwd", "coot_net_grads_overwrite", "coot_nets_zero_grads", "coot_nets_zero_grads_ex", "coot_debug_written_matrices", "coot_pack_fwd",
     "coot_pack_bwd", "coot_contrastive_scratch_bytes", "coot_contrastive_fwd_bwd", "coot_contrastive_fwd_bwd_part", "coot_contrastive_f32_scratch_bytes", "coot_contrastive_fwd_bwd_f32", "coot_cyclecons_fwd_bwd",
-    "coot_gemm_nt", "coot_debug_gemm_nt", "coot_gemm_tn", "coot_gemm_tn_batch", "coot_debug_tn_xcd_map", "coot_debug_clock_monitor", "coot_gemm_tn_workspace_bytes", "coot_ln_fwd", "coot_attn_fwd", "coot_debug_attn", "coot_probe_tr16", "coot_timing_enable",
+    "coot_gemm_nt", "coot_debug_gemm_nt", "coot_gemm_tn", "coot_gemm_tn_batch", "coot_debug_tn_xcd_map", "coot_debug_clock_monitor", "coot_gemm_tn_workspace_bytes", "coot_ln_fwd", "coot_attn_fwd", "coot_debug_attn", "coot_debug_ln", "coot_debug_pool", "coot_debug_avgpool", "coot_debug_avgpool_bwd", "coot_debug_pack_bwd_join", "coot_debug_colsum_bf16", "coot_probe_tr16", "coot_timing_enable",
     "coot_timing_collect", "coot_step_workspace_bytes", "coot_train_step", "coot_step_forward", "coot_step_backward",
     "coot_adam_step", "coot_radam_step", "coot_step_update", "coot_step_set_global_done_events", "coot_step_device_state_bytes", "coot_step_set_device_state", "coot_step_loss_scaler_bytes", "coot_step_set_loss_scaler", "coot_step_unscale_grads", "coot_step_grad_clip_bytes", "coot_step_set_grad_clip", "coot_step_grad_norm", "coot_collate_level", "coot_collate_packed", "coot_sample_cycle_indices", "coot_step_set_cycle_indices", "coot_step_input_stage_bytes", "coot_step_set_input_stages", "coot_step_set_next_batch", "coot_contrastive_fwd_bwd_dp", "coot_contrastive_fwd_bwd_dp_blocks", "coot_retrieval_workspace_bytes", "coot_retrieval_ranks", "coot_retrieval_topk_workspace_bytes", "coot_retrieval_topk",
     "coot_retrieval_ranks_part_workspace_bytes", "coot_retrieval_ranks_part", "coot_retrieval_metrics",
@@ -113,6 +113,31 @@ class AttnArgs(C.Structure):
                 ("dout", C.c_void_p), ("lddo", C.c_int64), ("delta", C.c_void_p),
                 ("dq", C.c_void_p), ("lddq", C.c_int64), ("dk", C.c_void_p), ("lddk", C.c_int64), ("dv", C.c_void_p), ("lddv", C.c_int64),
                 ("p", C.c_float), ("seed", C.c_uint64), ("site", C.c_uint)]
+
+
+class LnArgs(C.Structure):
+    """coot_ln_args: the LayerNorm forward and backward descriptors (sources, packed gather, pe, dropout, outputs) for coot_debug_ln."""
+    _fields_ = [("x", C.c_void_p), ("x_f32", C.c_int), ("ldx", C.c_int64), ("x2", C.c_void_p), ("R0", C.c_int), ("R", C.c_int), ("D", C.c_int),
+                ("gain", C.c_void_p), ("bias", C.c_void_p), ("pe", C.c_void_p), ("pe_L", C.c_int),
+                ("y", C.c_void_p), ("ldy", C.c_int64), ("y32", C.c_void_p), ("ldy32", C.c_int64),
+                ("p", C.c_float), ("seed", C.c_uint64), ("site", C.c_uint),
+                ("cu", C.c_void_p), ("nseq", C.c_int), ("N0", C.c_int), ("L0", C.c_int), ("L1", C.c_int), ("pos_out", C.c_void_p), ("src_packed", C.c_int),
+                ("max_wgs", C.c_int), ("nt", C.c_int),
+                ("dy", C.c_void_p), ("lddy", C.c_int64), ("dy32", C.c_void_p), ("lddy32", C.c_int64), ("dy_add", C.c_void_p), ("lddy_add", C.c_int64),
+                ("dx", C.c_void_p), ("lddx", C.c_int64), ("dx32", C.c_void_p), ("lddx32", C.c_int64), ("dxm", C.c_void_p), ("lddxm", C.c_int64),
+                ("pm", C.c_float), ("seed_m", C.c_uint64), ("site_m", C.c_uint), ("dxm_drop_ld", C.c_int64),
+                ("dgain", C.c_void_p), ("dbias", C.c_void_p), ("dxcolsum", C.c_void_p), ("part_ws", C.c_void_p), ("part_ws_floats", C.c_size_t)]
+
+
+class PoolArgs(C.Structure):
+    """coot_pool_args: one GenPool segment (packed rows, dropout, the hand-over to the padded layout) for coot_debug_pool."""
+    _fields_ = [("s", C.c_void_p), ("lds", C.c_int64), ("z", C.c_void_p), ("ldz", C.c_int64), ("lens", C.c_void_p), ("cu", C.c_void_p),
+                ("N", C.c_int), ("L", C.c_int), ("D", C.c_int), ("pooled", C.c_void_p), ("ldp", C.c_int64),
+                ("pooled_copy", C.c_void_p), ("smax", C.c_void_p), ("ssum", C.c_void_p),
+                ("p_w", C.c_float), ("seed_w", C.c_uint64), ("site_w", C.c_uint),
+                ("dpooled", C.c_void_p), ("lddp", C.c_int64), ("ds", C.c_void_p), ("ldds", C.c_int64), ("dz", C.c_void_p), ("lddz", C.c_int64),
+                ("ds_colsum", C.c_void_p), ("p_s", C.c_float), ("seed_s", C.c_uint64), ("site_s", C.c_uint), ("drop_s_ld", C.c_int64), ("drop_s_row0", C.c_int64),
+                ("pk_counts", C.c_void_p), ("pk_B", C.c_int), ("pk_Cmax", C.c_int), ("pk_out", C.c_void_p), ("pk_mask", C.c_void_p), ("pk_lens", C.c_void_p)]
 
 
 class PackedSeqs(C.Structure):
@@ -294,6 +319,13 @@ def load():
     lib.coot_ln_fwd.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
     lib.coot_attn_fwd.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp]
     lib.coot_debug_attn.argtypes = [C.POINTER(AttnArgs), i32, vp]
+    lib.coot_debug_ln.argtypes = [C.POINTER(LnArgs), i32, vp]
+    lib.coot_debug_pool.argtypes = [C.POINTER(PoolArgs), i32, i32, vp, sz, i32, vp]
+    lib.coot_debug_avgpool.argtypes = [vp, i64, vp, i32, i32, i32, vp, i64, vp]
+    lib.coot_debug_avgpool_bwd.argtypes = [vp, i64, vp, i32, i32, i32, vp, i64, vp]
+    lib.coot_debug_pack_bwd_join.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    lib.coot_debug_colsum_bf16.argtypes = [vp, i64, i32, i32, vp, vp, sz, vp]
+    lib.coot_debug_dropout_scales.argtypes = [u64, C.c_uint, u64, i64, f32, vp]
     lib.coot_probe_tr16.argtypes = [vp, vp]
     lib.coot_timing_enable.argtypes = [i32]
     lib.coot_timing_collect.argtypes = [i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)]

@@ -1134,6 +1134,73 @@ typedef struct coot_attn_args {
   float p; uint64_t seed; unsigned site;
 } coot_attn_args;
 int coot_debug_attn(const coot_attn_args* a, int backward, coot_stream_t stream);
+/* The whole LayerNorm descriptors the networks use (tests): launch_ln_fwd (backward == 0) or launch_ln_bwd on them.
+ * y = gain (x - mean) / (std_unbiased + 1e-6) + bias (gain NULL: no affine), + pe[(row % pe_L) D + col], times the dropout mask of
+ * (seed, site) at element row D + col (p quantised as coot_debug_dropout_scales does), to y (16-bit) and / or y32.  x is fp32
+ * (x_f32 != 0) or 16-bit.  x2: rows R0 .. R - 1 are rows 0 .. of x2.  cu (int32 [nseq + 1] row starts): output row r is token
+ * r - cu[n] of sequence n, read from row n L0 + l of x (n < N0) or (n - N0) L1 + l of x2, or from row r of x with src_packed;
+ * pos_out[r] = l.  max_wgs > 0 or nt != 0: the row-walking kernel of the input stages.  Backward (D <= 1024): dy (16-bit) or dy32,
+ * plus dy_add, times the forward's mask (p, seed, site), gives dx (16-bit), dx32, dxm = dx times the mask of (seed_m, site_m) at
+ * element row dxm_drop_ld + col; dgain, dbias, dxcolsum (column sums of dxm if set, else of dx) are ADDED to; any of them may be
+ * NULL.  part_ws (optional): the partial-sum workspace a network call would provide.  Strides in elements, multiples of 4. */
+typedef struct coot_ln_args {
+  const void* x; int x_f32; int64_t ldx;
+  const void* x2; int R0;
+  int R, D;
+  const float* gain; const float* bias;
+  const float* pe; int pe_L;
+  void* y; int64_t ldy;
+  float* y32; int64_t ldy32;
+  float p; uint64_t seed; unsigned site;
+  const int* cu; int nseq, N0, L0, L1; int* pos_out; int src_packed;
+  int max_wgs, nt;
+  const void* dy; int64_t lddy;
+  const float* dy32; int64_t lddy32;
+  const void* dy_add; int64_t lddy_add;
+  void* dx; int64_t lddx;
+  float* dx32; int64_t lddx32;
+  void* dxm; int64_t lddxm;
+  float pm; uint64_t seed_m; unsigned site_m; int64_t dxm_drop_ld;
+  float* dgain; float* dbias; float* dxcolsum;
+  float* part_ws; size_t part_ws_floats;
+} coot_ln_args;
+int coot_debug_ln(const coot_ln_args* a, int backward, coot_stream_t stream);
+/* One or two GenPool segments (tests): launch_pool_fwd2 / launch_pool_bwd2.  Per sequence n and channel: rows >= lens[n] of the L
+ * padded rows count as scores of -32752; w = softmax of s over the rows; pooled = sum_l w m_w z with m_w the dropout mask of
+ * (seed_w, site_w) at element (first row + l) D + channel; smax / ssum: the maximum and sum exp(s - max).  cu: sequence n is rows
+ * cu[n] .. cu[n] + lens[n] - 1, without padding rows.  pk_*: pooled rows also go to pk_out [pk_B, pk_Cmax, D] by pk_counts (zero
+ * padded), pk_mask (1 = padding), pk_lens.  Backward: reads smax, ssum, pooled; ds = w (dpooled z m_w - dpooled pooled) m_s with m_s
+ * the mask of (seed_s, site_s) at element (drop_s_row0 + row) drop_s_ld + channel; dz = dpooled w m_w; padded rows zero;
+ * ds_colsum += column sums of ds (through part_ws if given; inside a deferred-reduction scope with defer != 0). */
+typedef struct coot_pool_args {
+  const void* s; int64_t lds;
+  const void* z; int64_t ldz;
+  const int64_t* lens; const int* cu;
+  int N, L, D;
+  float* pooled; int64_t ldp;
+  float* pooled_copy; float* smax; float* ssum;
+  float p_w; uint64_t seed_w; unsigned site_w;
+  const float* dpooled; int64_t lddp;
+  void* ds; int64_t ldds;
+  void* dz; int64_t lddz;
+  float* ds_colsum;
+  float p_s; uint64_t seed_s; unsigned site_s; int64_t drop_s_ld, drop_s_row0;
+  const int64_t* pk_counts; int pk_B, pk_Cmax;
+  float* pk_out; uint8_t* pk_mask; int64_t* pk_lens;
+} coot_pool_args;
+int coot_debug_pool(const coot_pool_args* segs, int nseg, int backward, float* part_ws, size_t part_ws_floats, int defer,
+                    coot_stream_t stream);
+/* avg_special: out[n] = sum over ALL L rows of z / lens[n]; backward: every one of the L rows of dz = dpooled[n] / lens[n] */
+int coot_debug_avgpool(const void* z, int64_t ldz, const int64_t* lens, int N, int L, int D, float* out, int64_t ldo,
+                       coot_stream_t stream);
+int coot_debug_avgpool_bwd(const float* dpooled, int64_t lddp, const int64_t* lens, int N, int L, int D, void* dz, int64_t lddz,
+                           coot_stream_t stream);
+/* demb_items[ptr_b + c] += dout1[b, c] (+ dout2[b, c]) for c < counts[b]; demb_ctx[b] += dctx[b] (dout2, dctx optional) */
+int coot_debug_pack_bwd_join(const float* dout1, const float* dout2, const float* dctx, const int64_t* counts, int B, int Cmax,
+                             int D, float* demb_items, float* demb_ctx, coot_stream_t stream);
+/* out[c] += sum_r x[r, c] (x 16-bit); part_ws as in coot_debug_ln */
+int coot_debug_colsum_bf16(const void* x, int64_t ldx, int R, int C, float* out, float* part_ws, size_t part_ws_floats,
+                           coot_stream_t stream);
 /* HIP-event timing of every gemm_nt launch (the dominant kernel) while enabled; collect() synchronises the
  * recorded events and returns summed duration [ms], algorithmic flops (2*M*N*K) and launch count.
  * only_big_k != 0 restricts to the input-FC instances (K >= 1024). */
