@@ -20,7 +20,9 @@ from .retrieval import (RETRIEVAL_FEW_MAX, GalleryIndex, compute_retrieval, comp
                         compute_retrieval_topk_masked, compute_retrieval_topk_multi, compute_retrieval_topk_scoped, retrieval_metrics_device,
                         retrieval_range_device, retrieval_ranks_labeled_device, retrieval_ranks_part_device, retrieval_topk_device, retrieval_topk_grouped_device,
                         retrieval_topk_index_device, retrieval_topk_multi_device, retrieval_topk_scoped_device,
-                        compute_retrieval_topk_adjusted, compute_retrieval_hub_offsets, retrieval_topk_adjusted_device)
+                        compute_retrieval_topk_adjusted, compute_retrieval_hub_offsets, retrieval_topk_adjusted_device,
+                        compute_retrieval_labeled_adjusted, retrieval_ranks_adjusted_device, compute_retrieval_adjusted_device,
+                        compute_retrieval_csls_device)
 from .trainer_retrieval import GradClip, LossScaler, RetrievalTrainer, make_optimizer  # noqa: F401
 from .validation import loader_order_permutation, save_embeddings, shard_batch_indices  # noqa: F401
 from . import lr_scheduler  # noqa: F401,E402

@@ -659,7 +659,7 @@ extern "C" int coot_step_text_ahead_get(void);
 extern "C" int coot_internal_text_ahead_steps(void);
 extern "C" int coot_internal_stream_counter(int which);  // api_step.hip: StreamPicker
 extern "C++" { namespace coot { int det_bypass_count(); int det_overflow_count(); int det_set_overflow_guard(int on); int det_overflow_guard(); } }  // det.hip
-extern "C++" { namespace coot { void set_rt_topk_splits(int n); int get_rt_topk_splits(); void set_rt_few_splits(int n); int get_rt_few_splits(); void set_rt_grouped_splits(int n); int get_rt_grouped_splits(); void set_rt_knn_splits(int n); int get_rt_knn_splits(); void set_rt_comp_blocks_per_wg(int n); int get_rt_comp_blocks_per_wg(); } }  // retrieval_tile.hip, retrieval_few.hip, retrieval_grouped.hip, retrieval_knn.hip, retrieval_components.hip
+extern "C++" { namespace coot { void set_rt_topk_splits(int n); int get_rt_topk_splits(); void set_rt_few_splits(int n); int get_rt_few_splits(); void set_rt_grouped_splits(int n); int get_rt_grouped_splits(); void set_rt_knn_splits(int n); int get_rt_knn_splits(); void set_rt_comp_blocks_per_wg(int n); int get_rt_comp_blocks_per_wg(); void set_rt_adjusted_tile_splits(int n); int get_rt_adjusted_tile_splits(); } }  // retrieval_tile.hip, retrieval_few.hip, retrieval_grouped.hip, retrieval_knn.hip, retrieval_components.hip, retrieval_adjusted_tile.hip
 int coot_get_option(const char* name, int* value) {
   if (!value) { set_error("get_option: null result"); return -1; }
   if (!strcmp(name, "tn_dma")) { *value = get_tn_dma(); return 0; }
@@ -687,6 +687,7 @@ int coot_get_option(const char* name, int* value) {
   if (!strcmp(name, "rt_grouped_splits")) { *value = get_rt_grouped_splits(); return 0; }
   if (!strcmp(name, "rt_knn_splits")) { *value = get_rt_knn_splits(); return 0; }
   if (!strcmp(name, "rt_comp_blocks_per_wg")) { *value = get_rt_comp_blocks_per_wg(); return 0; }
+  if (!strcmp(name, "rt_adjusted_tile_splits")) { *value = get_rt_adjusted_tile_splits(); return 0; }
   set_error("get_option: unknown or write-only option %s", name);
   return -2;
 }
@@ -723,6 +724,7 @@ int coot_set_option(const char* name, int value) {
   if (!strcmp(name, "rt_grouped_splits")) { set_rt_grouped_splits(value); return 0; }  // (tests) ranges of the group table in coot_retrieval_topk_grouped's selection, 0 = automatic; the result does not depend on it
   if (!strcmp(name, "rt_knn_splits")) { set_rt_knn_splits(value); return 0; }  // (tests) shares of the right gallery in coot_retrieval_knn_join, 0 = automatic; the result does not depend on it
   if (!strcmp(name, "rt_comp_blocks_per_wg")) { set_rt_comp_blocks_per_wg(value); return 0; }  // (tests) 128-row blocks a workgroup of coot_retrieval_components walks, 0 = automatic; the result does not depend on it
+  if (!strcmp(name, "rt_adjusted_tile_splits")) { set_rt_adjusted_tile_splits(value); return 0; }  // (tests) shares of the gallery in coot_retrieval_topk_adjusted_tile, 0 = automatic; the result does not depend on it
   set_error("unknown option %s", name);
   return -2;
 }

@@ -8,7 +8,7 @@ mkdir -p "$OUT" obj
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -munsafe-fp-atomics -Wno-unused-result $EXTRA_FLAGS"
 # two builds of the same sources: bfloat16 operands (libcoot_hip.so, what bench.py times) and IEEE half operands
 # (libcoot_hip_f16.so, -DCOOT_OPERAND_F16: common.h; forward-only, except the native step under a loss scaler)
-SRCS="gemm rowops attention pool loss loss_fused loss_f32 fused ref_f32 det retrieval_tile retrieval_few retrieval_grouped retrieval_multi retrieval_scoped retrieval_adjusted retrieval_range retrieval_range_tile retrieval_join retrieval_cross_join retrieval_knn retrieval_components retrieval_index host_input api api_loss api_step"
+SRCS="gemm rowops attention pool loss loss_fused loss_f32 fused ref_f32 det retrieval_tile retrieval_few retrieval_grouped retrieval_multi retrieval_scoped retrieval_adjusted retrieval_ranks_adjusted retrieval_adjusted_tile retrieval_range retrieval_range_tile retrieval_join retrieval_cross_join retrieval_knn retrieval_components retrieval_index host_input api api_loss api_step"
 build_one() {  # <obj dir> <output .so> <extra flags>
   local OBJ=$1 SO=$2 EXTRA=$3 pids=()
   mkdir -p $OBJ

@@ -11,6 +11,13 @@ namespace coot {
 // rt_norms_kernel<float> (retrieval_index.hip) on rows [0, Ma) of a, then [0, Nb) of b; the caller checks the launch
 void rt_launch_norms(const float* a, int Ma, const float* b, int Nb, int d, float* na, float* nb, hipStream_t st);
 
+// The head and the tail of the labelled ranking (retrieval_tile.hip) for the ranking under offsets (retrieval_ranks_adjusted.hip):
+// rt_lab_prepare_kernel (ranks = 0 or -1 and n_valid, from labels and best [N]) and rt_metrics_kernel<true> (hist [N + M], zeroed);
+// the caller checks the launch
+void rt_launch_lab_prepare(const int32_t* labels, const unsigned long long* best, int M, int N, int32_t* ranks_q, int32_t* ranks_g, int32_t* n_valid,
+                           hipStream_t st);
+void rt_launch_lab_metrics(const int32_t* ranks_q, const int32_t* ranks_g, int M, int N, int* hist, float* metrics, hipStream_t st);
+
 // The few-query sweep's plan and the launches of its kernels that the grouped search shares (retrieval_few.hip):
 // few_plan: row splits and the 128-row blocks each one sweeps (every split has at least one block; cap bounds S whatever the option says);
 // rt_few_launch_prep: rt_few_prep_kernel, the query norms [16] and the operand table qn [d rounded up to 32][16];

@@ -656,6 +656,15 @@ LabWs lab_layout(void* base, int M, int N) {
 }
 
 }  // namespace
+// rt_lab_prepare_kernel and rt_metrics_kernel<true> for the labelled ranking under offsets (retrieval_ranks_adjusted.hip)
+void rt_launch_lab_prepare(const int32_t* labels, const unsigned long long* best, int M, int N, int32_t* ranks_q, int32_t* ranks_g, int32_t* n_valid,
+                           hipStream_t st) {
+  hipLaunchKernelGGL(rt_lab_prepare_kernel, dim3(1), dim3(1024), 0, st, (const int*)labels, (const tk_entry_t*)best, M, N, (int*)ranks_q, (int*)ranks_g,
+                     (int*)n_valid);
+}
+void rt_launch_lab_metrics(const int32_t* ranks_q, const int32_t* ranks_g, int M, int N, int* hist, float* metrics, hipStream_t st) {
+  hipLaunchKernelGGL(rt_metrics_kernel<true>, dim3(2), dim3(1024), 0, st, (const int*)ranks_q, (const int*)ranks_g, M, N, hist, metrics);
+}
 void set_rt_topk_splits(int n) { g_rt_topk_splits = n; }
 int get_rt_topk_splits() { return g_rt_topk_splits; }
 }  // namespace coot

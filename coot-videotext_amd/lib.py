@@ -40,6 +40,8 @@ EXPORTS = [
     "coot_retrieval_topk_multi_workspace_bytes", "coot_retrieval_topk_multi",
     "coot_retrieval_topk_scoped_workspace_bytes", "coot_retrieval_topk_scoped",
     "coot_retrieval_topk_adjusted_workspace_bytes", "coot_retrieval_topk_adjusted", "coot_retrieval_hub_offsets",
+    "coot_retrieval_topk_adjusted_tile_workspace_bytes", "coot_retrieval_topk_adjusted_tile",
+    "coot_retrieval_ranks_adjusted_workspace_bytes", "coot_retrieval_ranks_adjusted",
     "coot_retrieval_range_workspace_bytes", "coot_retrieval_range_count", "coot_retrieval_range_scan", "coot_retrieval_range_fill",
     "coot_retrieval_range_tile_workspace_bytes", "coot_retrieval_range_tile_count", "coot_retrieval_range_tile_fill",
     "coot_retrieval_join_count", "coot_retrieval_join_fill",
@@ -275,6 +277,12 @@ def load():
     lib.coot_retrieval_topk_adjusted_workspace_bytes.restype = C.c_size_t
     lib.coot_retrieval_topk_adjusted.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, C.c_size_t, vp]
     lib.coot_retrieval_hub_offsets.argtypes = [vp, vp, i32, i32, vp, vp]
+    lib.coot_retrieval_topk_adjusted_tile_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    lib.coot_retrieval_topk_adjusted_tile_workspace_bytes.restype = C.c_size_t
+    lib.coot_retrieval_topk_adjusted_tile.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.coot_retrieval_ranks_adjusted_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.coot_retrieval_ranks_adjusted_workspace_bytes.restype = C.c_size_t
+    lib.coot_retrieval_ranks_adjusted.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.coot_retrieval_range_workspace_bytes.argtypes = [i32, i32, i32]
     lib.coot_retrieval_range_workspace_bytes.restype = C.c_size_t
     lib.coot_retrieval_range_count.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, C.c_size_t, vp]

@@ -17,7 +17,8 @@ groups for a PARAGRAPH of queries (compute_retrieval_topk_multi): coot_retrieval
 GalleryIndex.search_scoped: every query inside (only=) or outside (exclude=) the rows with the id it brings
 (compute_retrieval_topk_scoped): coot_retrieval_topk_scoped; GalleryIndex.neighbors: a row's neighbours outside its own group.
 retrieval_topk_adjusted_device / GalleryIndex.search_adjusted: a number per gallery row taken off its similarity before the selection
-(compute_retrieval_topk_adjusted): coot_retrieval_topk_adjusted; GalleryIndex.hubness_offsets: the offsets that make it rank by CSLS
+(compute_retrieval_topk_adjusted): coot_retrieval_topk_adjusted in slices of 16 and, from ADJUSTED_TILE_MIN_M* queries on, one call of
+coot_retrieval_topk_adjusted_tile (_topk_adjusted); GalleryIndex.hubness_offsets: the offsets that make it rank by CSLS
 (compute_retrieval_hub_offsets): coot_retrieval_knn_join against a bank of queries, then coot_retrieval_hub_offsets.
 retrieval_range_device / GalleryIndex.search_range, count_range: every row at or above a query's threshold, however many, as CSR
 (compute_retrieval_range): coot_retrieval_range_count, _scan, _fill for up to RANGE_TILE_MIN_M* - 1 queries, in slices of 16, and
@@ -39,7 +40,9 @@ removed rows dropped — the index then holds, byte for byte, what a fresh index
 
 Sharded validation (data-parallel runs): retrieval_ranks_part_device counts one strip of rows, an integer all-reduce of the
 strips is the whole (compute_retrieval_device(dp=...)), retrieval_metrics_device turns rank vectors into the metrics.
-Labelled ranking (retrieval_ranks_labeled_device / compute_retrieval_labeled_device): compute_retrieval_labeled on the device."""
+Labelled ranking (retrieval_ranks_labeled_device / compute_retrieval_labeled_device): compute_retrieval_labeled on the device; under a
+number per gallery row and per query (retrieval_ranks_adjusted_device / compute_retrieval_adjusted_device: compute_retrieval_labeled_adjusted,
+coot_retrieval_ranks_adjusted), and compute_retrieval_csls_device: the metrics of a validation pair under CSLS."""
 from __future__ import annotations
 
 import numpy as np
@@ -48,7 +51,7 @@ from .retrieval_mirror import (VALKEYS, _ahead, _host_offsets, _labeled_metrics,
                                compute_retrieval_counts_part, compute_retrieval_labeled, compute_retrieval_topk, compute_retrieval_topk_grouped,
                                compute_retrieval_range, compute_retrieval_topk_masked, compute_retrieval_topk_multi, compute_retrieval_topk_scoped,
                                compute_retrieval_self_join, compute_retrieval_components, compute_retrieval_join, compute_retrieval_knn_join,
-                               compute_retrieval_topk_adjusted, compute_retrieval_hub_offsets, strip_bounds)
+                               compute_retrieval_topk_adjusted, compute_retrieval_hub_offsets, compute_retrieval_labeled_adjusted, strip_bounds)
 
 
 def _ptr(t):
@@ -415,8 +418,24 @@ def _check_offset(fn: str, offset, n: int, dev):
         return np.array(t.astype(np.float32))  # (a copy: contiguous and writable)
 
 
+# The adjusted search: from this many queries on, one tile call over all queries (coot_retrieval_topk_adjusted_tile, 64 queries per
+# workgroup and read of a gallery block); below it, slices of RETRIEVAL_FEW_MAX queries through the sweep, one sweep of the gallery
+# each.  ADJUSTED_TILE_MIN_M: a float32 gallery; ADJUSTED_TILE_MIN_M_16BIT: bfloat16 / float16.  Both routes return the same bytes.
+# Read at call time.  ADJUSTED_TILE_NEVER: above every M, the slices always serve.
+# Each is the smallest M of the measured ladder (profiles/r35_adjusted_tile.json: M = 17, 32, 64, 128, 256, 320, 512, 1 024; 200 000 x 768
+# and 18 000 x 384; K = 10) from which the tile route's median stays below the slices' median by more than the slices' own spread at both
+# galleries and at every larger M.  The tile walk takes 5.6 - 6.4 ms at 200 000 x 768 whatever M is up to 512, so it loses up to and
+# including 256 queries there (6.37 against 6.05 +- 0.10 ms on float32, 6.37 against 6.67 +- 1.06 ms on bfloat16: inside the spread) and wins
+# from 320 (6.41 against 7.49 and 6.39 against 8.59 ms); at 18 000 x 384 it already wins from 128 (0.84 against 1.10 and 1.26 ms), which
+# this one threshold leaves to the slices.
+ADJUSTED_TILE_NEVER = 1 << 31
+ADJUSTED_TILE_MIN_M = 320
+ADJUSTED_TILE_MIN_M_16BIT = 320
+
+
 def _topk_adjusted(queries, gallery, norms, offset, k: int, keep, want_sim: bool, method=None, own_keep=None):
-    """coot_retrieval_topk_adjusted for any M: slices of RETRIEVAL_FEW_MAX queries over one workspace.  Checked in this order: keep, the
+    """coot_retrieval_topk_adjusted for any M: slices of RETRIEVAL_FEW_MAX queries over one workspace; from ADJUSTED_TILE_MIN_M (float32
+    gallery) / ADJUSTED_TILE_MIN_M_16BIT queries on, one call of coot_retrieval_topk_adjusted_tile instead.  Checked in this order: keep, the
     offset, then where everything lives, the widths and k.  method, own_keep: the name and the own filter of GalleryIndex.search_adjusted."""
     import torch
     from . import lib as _lib
@@ -432,9 +451,15 @@ def _topk_adjusted(queries, gallery, norms, offset, k: int, keep, want_sim: bool
     offset = torch.from_numpy(offset).to(queries.device) if isinstance(offset, np.ndarray) else offset.contiguous()
     keep = _and_own(own_keep, keep)
     lib = _lib.load()
+    st = _stream()
+    if m >= (ADJUSTED_TILE_MIN_M_16BIT if code else ADJUSTED_TILE_MIN_M):  # one call, all queries
+        ws, idx, scores, sim = _topk_buffers(lib.coot_retrieval_topk_adjusted_tile_workspace_bytes(m, n, d, k), m, n, k, want_sim, queries.device)
+        _lib.check(lib.coot_retrieval_topk_adjusted_tile(queries.data_ptr(), gallery.data_ptr(), code, _ptr(norms), _ptr(keep), offset.data_ptr(), m, n,
+                                                         d, k, idx.data_ptr(), scores.data_ptr(), _ptr(sim), ws.data_ptr(), ws.numel(), st),
+                   "coot_retrieval_topk_adjusted_tile")
+        return idx, scores, sim
     ws, idx, scores, sim = _topk_buffers(lib.coot_retrieval_topk_adjusted_workspace_bytes(min(m, RETRIEVAL_FEW_MAX), n, d, k), m, n, k, want_sim,
                                          queries.device)
-    st = _stream()
     for i in range(0, m, RETRIEVAL_FEW_MAX):  # the calls of a stream run in order: one workspace
         mm = min(RETRIEVAL_FEW_MAX, m - i)
         _lib.check(lib.coot_retrieval_topk_adjusted(queries[i:].data_ptr(), gallery.data_ptr(), code, _ptr(norms), _ptr(keep), offset.data_ptr(), mm, n,
@@ -455,7 +480,8 @@ def retrieval_topk_adjusted_device(queries, gallery, norms, offset, k: int, keep
     offset +inf scores -inf and is still returned, with its index, once nothing better is left (a masked row never is); -inf puts a
     row first.  With fewer than k kept rows the tail is idx -1, score -inf.  1 <= k <= min(N, 128), whatever keep holds.  Without
     sim, blocks of 128 rows in which keep leaves no row are not read.  Nothing synchronises.  More than 16 queries run in slices of
-    16, one sweep of the gallery each, over one workspace."""
+    16, one sweep of the gallery each, over one workspace; from ADJUSTED_TILE_MIN_M (float32 gallery) / ADJUSTED_TILE_MIN_M_16BIT
+    queries on, one call of coot_retrieval_topk_adjusted_tile serves them all, with the same bytes."""
     return _topk_adjusted(queries, gallery, norms, offset, k, keep, want_sim)
 
 
@@ -1375,8 +1401,8 @@ class GalleryIndex:
         a recency boost, a popularity prior or a calibration constant per source are offsets too.  offset +inf leaves a row with
         score -inf, still a row and returned last (ties to the larger row), unlike a masked one; -inf puts it first.  keep and the
         index's own filter (remove) combine as in search; with fewer than k kept rows the tail is idx -1, score -inf.  1 <= k <=
-        min(N, 128).  Nothing synchronises.  Any M: slices of 16 queries, one sweep of the gallery each
-        (retrieval_topk_adjusted_device).  The index does not store offsets; the caller owns the vector across add() (append to it)
+        min(N, 128).  Nothing synchronises.  Any M: slices of 16 queries, one sweep of the gallery each, or from ADJUSTED_TILE_MIN_M /
+        ADJUSTED_TILE_MIN_M_16BIT queries on one tile call, with the same bytes (retrieval_topk_adjusted_device).  The index does not store offsets; the caller owns the vector across add() (append to it)
         and compact() (offset[old_rows]), as for groups in search_grouped."""
         return _topk_adjusted(queries, self.gallery, self.norms if self.normalize else None, offset, k, keep, want_sim,
                               method="GalleryIndex.search_adjusted", own_keep=self.keep)
@@ -1641,6 +1667,92 @@ def compute_retrieval_labeled_device(queries, gallery, labels, normalize: bool =
     """Device version of compute_retrieval_labeled for embeddings (not a similarity matrix): (res_q2g, res_g2q, sum_at_1) with the
     reference's dictionary keys, as compute_retrieval_device returns them.  One 56-byte D2H copy."""
     return _metric_dicts(retrieval_ranks_labeled_device(queries, gallery, labels, normalize)[3])
+
+
+def retrieval_ranks_adjusted_device(queries, gallery, labels, col_offset=None, row_offset=None, normalize: bool = False, want_sim: bool = False):
+    """retrieval_ranks_labeled_device under offsets (coot_retrieval_ranks_adjusted): queries [M, d], gallery [N, d]: cuda float32; labels:
+    cuda int32 [M]; col_offset: None, a cuda torch.float32 tensor [N] or N numbers on the host (a sequence, a numpy array or a CPU
+    tensor, rounded to float32 once and uploaded once), the offset of GalleryIndex.search_adjusted; row_offset: the same with M numbers,
+    one per query.  Returns (ranks_q int32 [M], ranks_g int32 [N], n_valid int32 [2], metrics float32 [2, 7], sim [M, N] or None), all
+    on the device (no synchronisation): compute_retrieval_labeled_adjusted of the fp32 similarities retrieval_ranks_labeled_device counts
+    on, byte for byte, a(i, j) = (s(i, j) - col[j]) - row[i], without the M x N matrix (want_sim is a testing aid and holds the raw s).
+    Without offsets, and with zeros, the bytes of retrieval_ranks_labeled_device.  Checked on the host before anything is launched
+    (ValueError): two float32 matrices of one width, int32 labels [M], the offsets' type, shape and device; then that everything lives
+    on the device (RuntimeError naming the mirror)."""
+    import torch
+    from . import lib as _lib
+    fn, mirror = "retrieval_ranks_adjusted_device", "compute_retrieval_labeled_adjusted"
+    for name, t in (("queries", queries), ("gallery", gallery)):
+        if not isinstance(t, torch.Tensor) or t.dtype is not torch.float32 or t.dim() != 2:
+            raise ValueError(f"{fn}: {name} has to be a torch.float32 tensor of two dimensions, not {getattr(t, 'dtype', type(t).__name__)} "
+                             f"of shape {tuple(getattr(t, 'shape', ()))}")
+    (m, d), n = queries.shape, gallery.shape[0]
+    if gallery.shape[1] != d:
+        raise ValueError(f"{fn}: queries of width {d}, gallery of width {gallery.shape[1]}")
+    if m < 1 or n < 1 or d < 1:
+        raise ValueError(f"{fn}: M = {m}, N = {n}, d = {d}; each has to be at least 1")
+    if not isinstance(labels, torch.Tensor) or labels.dtype is not torch.int32 or tuple(labels.shape) != (m,):
+        raise ValueError(f"{fn}: labels has to be a torch.int32 tensor [{m}] (one gallery row per query), not "
+                         f"{getattr(labels, 'dtype', type(labels).__name__)} of shape {tuple(getattr(labels, 'shape', ()))}")
+    col = None if col_offset is None else _check_offset(f"{fn} (col_offset)", col_offset, n, gallery.device)
+    row = None if row_offset is None else _check_offset(f"{fn} (row_offset)", row_offset, m, gallery.device)
+    _on_device(fn, mirror, queries, gallery, labels)
+    if queries.device != gallery.device or labels.device != gallery.device:
+        raise ValueError(f"{fn}: queries live on {queries.device}, labels on {labels.device}, the gallery on {gallery.device}")
+    queries, gallery, labels = queries.contiguous(), gallery.contiguous(), labels.contiguous()
+    dev = queries.device
+    col, row = [None if o is None else torch.from_numpy(o).to(dev) if isinstance(o, np.ndarray) else o.contiguous() for o in (col, row)]
+    lib = _lib.load()
+    ws = torch.empty(lib.coot_retrieval_ranks_adjusted_workspace_bytes(m, n, d), dtype=torch.uint8, device=dev)
+    ranks_q = torch.empty(m, dtype=torch.int32, device=dev)
+    ranks_g = torch.empty(n, dtype=torch.int32, device=dev)
+    n_valid = torch.empty(2, dtype=torch.int32, device=dev)
+    met = torch.empty(2, 7, dtype=torch.float32, device=dev)
+    sim = torch.empty(m, n, dtype=torch.float32, device=dev) if want_sim else None
+    _lib.check(lib.coot_retrieval_ranks_adjusted(queries.data_ptr(), gallery.data_ptr(), labels.data_ptr(), _ptr(row), _ptr(col), m, n, d, int(normalize),
+                                                 ranks_q.data_ptr(), ranks_g.data_ptr(), n_valid.data_ptr(), met.data_ptr(), _ptr(sim), ws.data_ptr(),
+                                                 ws.numel(), _stream()), "coot_retrieval_ranks_adjusted")
+    return ranks_q, ranks_g, n_valid, met, sim
+
+
+def compute_retrieval_adjusted_device(queries, gallery, labels, col_offset=None, row_offset=None, normalize: bool = False):
+    """Device version of compute_retrieval_labeled_adjusted for embeddings (not a similarity matrix): (res_q2g, res_g2q, sum_at_1) with
+    the reference's dictionary keys, as compute_retrieval_labeled_device returns them.  One 56-byte D2H copy."""
+    return _metric_dicts(retrieval_ranks_adjusted_device(queries, gallery, labels, col_offset, row_offset, normalize)[3])
+
+
+def compute_retrieval_csls_device(emb1, emb2, k: int = 10, labels=None):
+    """The retrieval metrics of a validation pair under CSLS, the hubness correction in both directions: (res_1to2, res_2to1, sum_at_1)
+    with the reference's dictionary keys.  emb1 [M, d] (the queries), emb2 [N, d] (the gallery): cuda float32; labels: cuda int32 [M],
+    labels[i] = the row of emb2 that belongs to row i of emb1, or None: arange (M == N, the ground truth on the diagonal).  Both sides
+    are normalised; CSLS(i, j) = 2 s(i, j) - r_1(i) - r_2(j), r_1(i) the mean similarity of row i of emb1 to its k nearest rows of emb2
+    and r_2(j) the same for row j of emb2 in emb1, ranks as (s(i, j) - r_2(j) / 2) - r_1(i) / 2 does: two GalleryIndex(normalize=True)
+    that keep the embeddings by reference, row = idx1.hubness_offsets(idx2, k), col = idx2.hubness_offsets(idx1, k), then
+    compute_retrieval_adjusted_device(emb1, emb2, labels, col, row, normalize=True).  1 <= k <= min(M, N, 128).  Checked on the host
+    before anything is launched (ValueError).  One 56-byte D2H copy."""
+    import torch
+    fn = "compute_retrieval_csls_device"
+    for name, t in (("emb1", emb1), ("emb2", emb2)):
+        if not isinstance(t, torch.Tensor) or t.dtype is not torch.float32 or t.dim() != 2:
+            raise ValueError(f"{fn}: {name} has to be a torch.float32 tensor of two dimensions, not {getattr(t, 'dtype', type(t).__name__)} "
+                             f"of shape {tuple(getattr(t, 'shape', ()))}")
+    if emb1.shape[1] != emb2.shape[1]:
+        raise ValueError(f"{fn}: emb1 of width {emb1.shape[1]}, emb2 of width {emb2.shape[1]}")
+    m, n = emb1.shape[0], emb2.shape[0]
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= min(m, n, 128):
+        raise ValueError(f"{fn}: k = {k!r} is outside 1 .. min(M = {m}, N = {n}, 128)")
+    if labels is None and m != n:
+        raise ValueError(f"{fn}: labels=None puts the ground truth on the diagonal, which needs as many rows in emb1 ({m}) as in emb2 ({n})")
+    if labels is not None and (not isinstance(labels, torch.Tensor) or labels.dtype is not torch.int32 or tuple(labels.shape) != (m,)):
+        raise ValueError(f"{fn}: labels has to be None or a torch.int32 tensor [{m}], not {getattr(labels, 'dtype', type(labels).__name__)} "
+                         f"of shape {tuple(getattr(labels, 'shape', ()))}")
+    _on_device(fn, "compute_retrieval_labeled_adjusted", emb1, emb2, labels)
+    emb1, emb2 = emb1.contiguous(), emb2.contiguous()
+    idx1, idx2 = GalleryIndex(emb1, normalize=True), GalleryIndex(emb2, normalize=True)
+    row, col = idx1.hubness_offsets(idx2, int(k)), idx2.hubness_offsets(idx1, int(k))
+    if labels is None:
+        labels = torch.arange(m, dtype=torch.int32, device=emb1.device)
+    return compute_retrieval_adjusted_device(emb1, emb2, labels, col, row, normalize=True)
 
 
 def retrieval_ranks_part_device(emb1, emb2, row0: int, rows: int, normalize: bool = False, want_sim: bool = False):

@@ -16,6 +16,7 @@ compute_retrieval_join: the same on the similarities of two galleries, with a fi
 compute_retrieval_knn_join: the k best partners of every row under those filters, in the order of compute_retrieval_topk.
 compute_retrieval_labeled: ranks and metrics without the assumption "square, ground truth on the diagonal": labels[i] = the gallery
 row of query i; several queries per row, rows without a query and queries without a row (a label outside [0, N)) are allowed.
+compute_retrieval_labeled_adjusted: the same after a number per column and a number per row have been taken off every similarity.
 strip_bounds / compute_retrieval_counts_part: one strip of rows of the sharded validation; the sum over the strips is the whole."""
 from __future__ import annotations
 
@@ -477,6 +478,28 @@ def compute_retrieval_labeled(sim: np.ndarray, labels: np.ndarray):
     res_q, _ = _labeled_metrics(ranks_q)
     res_g, _ = _labeled_metrics(ranks_g)
     return res_q, res_g, ranks_q, ranks_g
+
+
+def compute_retrieval_labeled_adjusted(sim: np.ndarray, labels: np.ndarray, col_offset=None, row_offset=None):
+    """Host mirror of coot_retrieval_ranks_adjusted: compute_retrieval_labeled of the adjusted matrix a, with sim float32 [M, N],
+    col_offset [N] and row_offset [M] numbers (rounded to float32 once) or None.  a = sim without offsets; a = sim - col[None, :] with
+    col_offset; then a = a - row[:, None] with row_offset: one float32 subtraction each, the column's first.  col_offset is the offset
+    of compute_retrieval_topk_adjusted: with it alone ranks_q[i] is the position of labels[i] in compute_retrieval_topk_adjusted(sim,
+    col_offset, N)[0][i].  An offset of +inf leaves a = -inf: such a column is still a column and still a valid label.  A NaN in a
+    (inf - inf) is not modelled.  Returns (res_q2g, res_g2q, ranks_q int32 [M], ranks_g int32 [N])."""
+    sim = np.asarray(sim)
+    assert sim.ndim == 2 and sim.dtype == np.float32, (sim.shape, sim.dtype)
+    a = sim
+    with np.errstate(over="ignore", invalid="ignore"):
+        if col_offset is not None:
+            col = np.asarray(col_offset).astype(np.float32)
+            assert col.shape == (sim.shape[1],), (sim.shape, col.shape)
+            a = (a - col[None, :]).astype(np.float32)
+        if row_offset is not None:
+            row = np.asarray(row_offset).astype(np.float32)
+            assert row.shape == (sim.shape[0],), (sim.shape, row.shape)
+            a = (a - row[:, None]).astype(np.float32)
+    return compute_retrieval_labeled(a, labels)
 
 
 def strip_bounds(n: int, world: int, rank: int) -> Tuple[int, int]:

@@ -547,6 +547,27 @@ int coot_retrieval_topk_adjusted(const float* queries, const void* gallery, int 
                                  const float* offset, int M, int N, int d, int K, int32_t* idx_out, float* score_out, float* sim_out,
                                  void* workspace, size_t workspace_bytes, coot_stream_t stream);
 
+/* ---- adjusted search for a whole query set: one tile call -----------------------------------------------------------------------------
+ * coot_retrieval_topk_adjusted for any M in one call: the same arguments, the same definition and, for every query, the same bytes of
+ * idx_out, score_out [M, K] and sim_out [M, N] (optional: the raw s of every row, kept or not) as that call returns for the query in
+ * any slice of COOT_RETRIEVAL_FEW_MAX.  64 queries x one 128-row block of the gallery per step of a workgroup, the selection of
+ * coot_retrieval_knn_join behind the chain; offset[j] of a block waits in on-chip memory while the chain runs.  keep gates which rows
+ * are candidates, the offset gates nothing (+inf: score -inf, still a row).  Without sim_out a block of 128 rows in which keep leaves
+ * no row is not read at all; with it no block is skipped.
+ *   1 <= M, ceil(M / 64) <= 65 535, 1 <= K <= min(N, 128) (K is not checked against the mask);
+ *   gallery_dtype COOT_GALLERY_F32, _BF16 or _F16; gallery_norms NULL: rows used as they are, else the queries' norms are computed
+ *   here (one launch) and both sides are divided at staging.
+ * The gallery is cut into S shares (automatic: about 2 048 workgroups, no share under 8 blocks, at most 32;
+ * coot_set_option("rt_adjusted_tile_splits", n) fixes S for tests, 0 = automatic), S > 1 merged by rank; the result depends on neither S,
+ * the workgroup schedule nor a query's batch-mates.  workspace (16-byte aligned): coot_retrieval_topk_adjusted_tile_workspace_bytes(M,
+ * N, d, K), exact = M floats and, for S > 1, M x S x K 64-bit words, each rounded up to 256 bytes (0 for arguments out of range).  A
+ * refused call (unknown dtype, null pointer other than gallery_norms, keep and sim_out, M or K outside its range, workspace misaligned
+ * or too small) returns before any launch and writes nothing.  No allocation, no synchronisation; no pointer is retained. */
+size_t coot_retrieval_topk_adjusted_tile_workspace_bytes(int M, int N, int d, int K);
+int coot_retrieval_topk_adjusted_tile(const float* queries, const void* gallery, int gallery_dtype, const float* gallery_norms, const uint8_t* keep,
+                                      const float* offset, int M, int N, int d, int K, int32_t* idx_out, float* score_out, float* sim_out,
+                                      void* workspace, size_t workspace_bytes, coot_stream_t stream);
+
 /* ---- hubness offsets: the lists of a k-NN join into one number per row ---------------------------------------------------------------
  * scores (fp32), idx (int32): device [N][K], the lists coot_retrieval_knn_join wrote for the N gallery rows against a bank of
  * representative queries.  Per row j: c = the number of slots with idx >= 0 (the filled ones, a prefix); c > 0: acc = 0, then
@@ -783,6 +804,29 @@ size_t coot_retrieval_ranks_labeled_workspace_bytes(int M, int N, int d);
 int coot_retrieval_ranks_labeled(const float* queries, const float* gallery, const int32_t* labels, int M, int N, int d, int normalize,
                                  int32_t* ranks_q, int32_t* ranks_g, int32_t* n_valid, float* metrics, float* sim_out, void* workspace,
                                  size_t workspace_bytes, coot_stream_t stream);
+
+/* ---- labelled ranking under offsets: a number per gallery row and per query is taken off every similarity ----------------------------
+ * coot_retrieval_ranks_labeled on the adjusted matrix
+ *   a(i, j) = s(i, j)                       neither offset given
+ *   a(i, j) = s(i, j) - col[j]              col_offset given (device fp32 [N])
+ *   a(i, j) = (s(i, j) - col[j]) - row[i]   both given (row_offset: device fp32 [M]; alone: s(i, j) - row[i])
+ * s is bit for bit the sim_out of coot_retrieval_ranks_labeled, and sim_out here holds the same raw s; each subtraction is one IEEE
+ * fp32 subtraction after the chain, the column's first.  ranks_q, ranks_g, n_valid and metrics are those of
+ * coot_retrieval_ranks_labeled with a in the place of s: the same tie rule, labels outside [0, N) without ground truth, several queries
+ * per row, rows without a query, the best-ranked ground truth per gallery row.  col_offset is the offset of
+ * coot_retrieval_topk_adjusted: with it alone, ranks_q[i] < K holds exactly when labels[i] is among the K rows that search returns for
+ * query i, at that position.  An offset of +inf leaves a = -inf: a column at +inf is still a column and still a valid label; a NaN in
+ * a (inf - inf) has unspecified ranks.  Without offsets, and with zeros, every output is coot_retrieval_ranks_labeled's, byte for byte.
+ * A hubness correction in both directions (CSLS) is col = coot_retrieval_hub_offsets of the gallery against the queries and row = the
+ * same of the queries against the gallery.  Gallery and queries are fp32; normalize, M, N, d and the refusals as in
+ * coot_retrieval_ranks_labeled (null pointer other than the offsets, metrics and sim_out; ceil(M / 64) > 65 535; workspace misaligned
+ * or too small), before any launch: a refused call writes nothing.  Integer atomics only: nothing depends on the workgroup schedule.
+ * workspace (8-byte aligned): coot_retrieval_ranks_adjusted_workspace_bytes(M, N, d), exact, the layout of
+ * coot_retrieval_ranks_labeled.  The call retains no pointer and does not synchronise. */
+size_t coot_retrieval_ranks_adjusted_workspace_bytes(int M, int N, int d);
+int coot_retrieval_ranks_adjusted(const float* queries, const float* gallery, const int32_t* labels, const float* row_offset, const float* col_offset,
+                                  int M, int N, int d, int normalize, int32_t* ranks_q, int32_t* ranks_g, int32_t* n_valid, float* metrics,
+                                  float* sim_out, void* workspace, size_t workspace_bytes, coot_stream_t stream);
 
 /* ---- the whole training step as native code (coot/trainer_retrieval.py:253-291) -------------------------------
  * Networks are indexed 0 = net_video_local, 1 = net_video_global, 2 = net_text_local, 3 = net_text_global
